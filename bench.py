@@ -2,15 +2,28 @@
 
 Measures training graphs/sec (whole job) for the 8-layer/256-dim PERT-GNN on
 synthetic Alibaba-shaped call graphs, one process
-per GPU over RCCL, and appends the latency-MAE anchor (the second half of the
-BASELINE metric) from a short training run on an ingested synthetic dataset.
+per GPU over RCCL.  A plain run does only what that headline figure needs:
+set up, warm up, time the steps, print one JSON result line.  `--full` also
+appends the latency-MAE anchor (the second half of the BASELINE metric) from a
+short training run on an ingested synthetic dataset.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
         --master-addr 127.0.0.1 bench.py --gpus 8 --steps 20 --warmup 5
 
 (`python bench.py --gpus 8` without torchrun re-execs itself under
 torch.distributed.run with 8 local ranks.)
+
+`--dump-outputs DIR` writes what the last timed step computed (loss,
+predictions, gradients, updated parameters) as DIR/<name>.npy.  The batches and
+the initial weights are seeded, and with this option the last timed step starts
+again from that seeded initial model/optimizer state: the training kernels sum
+with atomics, and Adam's first steps amplify that 1-ulp ordering noise into a
+trajectory that differs from run to run, so only a step from a fixed state can
+be compared output for output between runs or builds.  The step itself, and
+what is timed, are the same with or without the option.
 
 Batches are pre-collated once and held resident on HBM (the north-star
 "graph-shard prefetch sized for 288 GB"); every timed step is a FULL training
@@ -184,6 +197,29 @@ def measure_latency_mae(epochs: int, device, seed: int = 7) -> dict:
             "mae_dataset_traces": len(data_list), "mae_model": "2conv/32H"}
 
 
+# --dump-outputs budget: every array is float32, at most _DUMP_MAX_ELEMS
+# elements each (5 arrays -> <= 40 MB in all, under the 64 MB cap)
+_DUMP_MAX_ELEMS = 2 * 1024 * 1024
+_DUMP_SAMPLE_SEED = 20230806
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each tensor as out_dir/<name>.npy (float32).  An array above the
+    per-array budget is reduced to a fixed, seeded sample of its flattened
+    elements (sorted indices — the same elements in every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        a = np.ascontiguousarray(a).reshape(-1) if a.ndim == 0 else a
+        if a.size > _DUMP_MAX_ELEMS:
+            rng = np.random.default_rng(_DUMP_SAMPLE_SEED)
+            idx = np.sort(rng.choice(a.size, _DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -204,8 +240,15 @@ def main():
                     default="auto", help="hipGraph stepping mode (see module doc)")
     ap.add_argument("--no-hipgraph", action="store_true",
                     help="disable hipGraph capture of the training step (= --graph-mode eager)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure "
+                         "(the latency-MAE anchor probe)")
     ap.add_argument("--mae-epochs", type=int, default=25,
-                    help="epochs for the latency-MAE anchor probe (0 = skip)")
+                    help="epochs for the latency-MAE anchor probe under "
+                         "--full (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's "
+                         "outputs as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     # `--gpus N` without a torchrun rendezvous: re-exec under
@@ -253,28 +296,45 @@ def main():
 
     model.train()
 
+    # --dump-outputs: the seeded initial training state (weights, Adam moments
+    # and step counters, BN running statistics), put back in place before the
+    # last timed step so that step's inputs are the same in every run
+    snapshot = None
+    if args.dump_outputs:
+        state = [optimizer.flat_param, optimizer.exp_avg, optimizer.exp_avg_sq,
+                 optimizer.dev_state, *model.buffers()]
+        snapshot = ([(t, t.detach().clone()) for t in state], optimizer.step_count)
+
+    @torch.no_grad()
+    def restore_snapshot():
+        for t, t0 in snapshot[0]:
+            t.copy_(t0)
+        optimizer.step_count = snapshot[1]
+
     def step_compute(i):
         """zero_grad + forward + loss + backward (no collectives unless the
         engine hooks are enabled)."""
         b = batches[i % len(batches)]
         optimizer.zero_grad(set_to_none=False)
-        gp, _ = model(b.x, b.cat_X, b.edge_index, b.edge_attr,
-                      b.pattern_num_nodes, b.rt_probs, b.entry_id, b.batch,
-                      csr=b.csr, num_graphs=b.num_graphs)
+        gp, lp = model(b.x, b.cat_X, b.edge_index, b.edge_attr,
+                       b.pattern_num_nodes, b.rt_probs, b.entry_id, b.batch,
+                       csr=b.csr, num_graphs=b.num_graphs)
         loss = F.quantile_loss(b.y, gp.flatten(), args.tau)
         loss.backward()
-        return loss
+        # detached: holding the outputs must not keep the autograd graph (and
+        # the activations it saved) alive past the step
+        return loss.detach(), gp.detach(), lp.detach()
 
     def step(i):
         """Full eager training step (bucketed all-reduce overlapped with
         backward via the engine hooks)."""
         if engine is not None:
             engine.reset()
-        loss = step_compute(i)
+        outs = step_compute(i)
         if engine is not None:
             engine.finalize()
         optimizer.step()
-        return loss
+        return outs
 
     mode = "eager" if args.no_hipgraph else args.graph_mode
     if mode == "auto":
@@ -291,23 +351,25 @@ def main():
             body(i)  # allocation warmup per batch shape
         torch.cuda.synchronize()
         gobjs = []
+        gouts = []  # each graph's static (loss, gp, lp), refilled per replay
         pool = None
         for i in range(len(batches)):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=pool):
-                body(i)
+                outs = body(i)
             if pool is None:
                 pool = g.pool()
             gobjs.append(g)
+            gouts.append(outs)
         torch.cuda.synchronize()
-        return gobjs
+        return gobjs, gouts
 
     timed_step = step
     level = 0
-    gobjs = None
+    gobjs = gouts = None
     if mode == "full":
         try:
-            gobjs = try_capture(step)
+            gobjs, gouts = try_capture(step)
             level = 2
         except Exception as exc:  # pragma: no cover - hardware path
             print(f"# full-step hipGraph capture unavailable ({exc}); "
@@ -318,7 +380,7 @@ def main():
             if engine is not None:
                 engine.enabled = False
             try:
-                gobjs = try_capture(step_compute)
+                gobjs, gouts = try_capture(step_compute)
             finally:
                 if engine is not None:
                     engine.enabled = True
@@ -333,6 +395,7 @@ def main():
     if level == 2:
         def timed_step(i):
             gobjs[i % len(gobjs)].replay()
+            return gouts[i % len(gobjs)]
     elif level == 1:
         inv_ws = 1.0 / comm.world_size
 
@@ -342,6 +405,7 @@ def main():
                 comm.all_reduce_(optimizer.flat_grad)
                 optimizer.flat_grad.mul_(inv_ws)
             optimizer.step()
+            return gouts[i % len(gobjs)]
     else:
         timed_step = step
     mode_used = {2: "full", 1: "split", 0: "eager"}[level]
@@ -353,8 +417,11 @@ def main():
     if on_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        timed_step(args.warmup + i)
+        if snapshot is not None and i == args.steps - 1:
+            restore_snapshot()
+        last = timed_step(args.warmup + i)
     comm.barrier()
     if on_gpu:
         torch.cuda.synchronize()
@@ -362,10 +429,19 @@ def main():
     # max over ranks
     elapsed = comm.all_reduce_scalar(elapsed, op="max")
 
-    # latency-MAE anchor (rank 0 only; the other ranks idle at the final
-    # barrier) — skipped on CPU to keep the no-GPU default run fast
+    # what the last timed step handed back: loss + predictions, and the
+    # gradients / updated parameters it left in the optimizer's flat buffers
+    if args.dump_outputs and comm.rank == 0 and last is not None:
+        loss, gp, lp = last
+        dump_outputs(args.dump_outputs, {
+            "loss": loss, "global_predict": gp, "local_predict": lp,
+            "flat_grad": optimizer.flat_grad, "flat_param": optimizer.flat_param,
+        })
+
+    # latency-MAE anchor, --full only (rank 0 only; the other ranks idle at
+    # the final barrier) — skipped on CPU to keep the no-GPU run fast
     mae_info = {"latency_mae": None}
-    if args.mae_epochs > 0 and on_gpu and comm.rank == 0:
+    if args.full and args.mae_epochs > 0 and on_gpu and comm.rank == 0:
         try:
             mae_info = measure_latency_mae(args.mae_epochs, device)
         except Exception as exc:  # pragma: no cover

@@ -386,6 +386,9 @@ def _worker_bench(rank, world_size, port, result_queue):
     import sys as _sys
     import contextlib
 
+    # gloo on CPU also where a GPU is present: two ranks cannot share one
+    # device under RCCL
+    torch.cuda.is_available = lambda: False
     argv = ["bench.py", "--steps", "2", "--warmup", "1", "--batch-size", "6",
             "--n-batches", "1", "--layers", "2", "--hidden", "32"]
     out = io.StringIO()
@@ -444,6 +447,8 @@ def _worker_cli_hipgraph(rank, world_size, port, workdir, result_queue):
             "32", "--seed", "3", "--hipgraph", "--sync_bn",
             "--processed_dir", os.path.join(workdir, "processed")]
     out = io.StringIO()
+    # gloo on CPU also where a GPU is present (see _worker_bench)
+    torch.cuda.is_available = lambda: False
     import pert_gnn
 
     with contextlib.redirect_stdout(out):

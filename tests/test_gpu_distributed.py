@@ -115,6 +115,71 @@ def test_bench_split_mode_gpu():
     assert rec["value"] > 0
 
 
+@pytest.mark.timeout(600)
+def test_bench_full_and_dump_outputs_gpu(tmp_path):
+    """bench.py --full on hardware: the latency-MAE anchor probe fills
+    `latency_mae`, and --dump-outputs hands back what the last replayed
+    whole-step hipGraph computed (static graph outputs + flat buffers)."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run(
+        [sys.executable, "bench.py", "--steps", "3", "--warmup", "1",
+         "--batch-size", "64", "--n-batches", "2", "--layers", "2",
+         "--hidden", "256", "--vocab", "small", "--full", "--mae-epochs", "1",
+         "--dump-outputs", str(tmp_path)],
+        capture_output=True, text=True, timeout=540, cwd=root,
+    )
+    assert out.returncode == 0, (out.stdout[-2000:], out.stderr[-2000:])
+    rec = json.loads(out.stdout.strip().splitlines()[-1])
+    assert rec["config"]["graph_mode"] == "full"
+    assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+    assert rec["latency_mae"] is not None and np.isfinite(rec["latency_mae"])
+    assert rec["mae_detail"]["mae_epochs"] == 1
+    arrs = {n: np.load(tmp_path / f"{n}.npy") for n in
+            ("loss", "global_predict", "local_predict", "flat_grad", "flat_param")}
+    for n, a in arrs.items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+    assert arrs["loss"].shape == (1,) and arrs["loss"][0] > 0
+    assert arrs["global_predict"].shape == (64, 1)
+    assert arrs["flat_grad"].shape == arrs["flat_param"].shape
+    assert np.abs(arrs["flat_grad"]).max() > 0
+
+    # A second run (more steps, ending on the same batch) dumps the same step
+    # from the same seeded state.  The kernels' atomic sums differ by fp32
+    # ulps between runs; where such a difference flips the rounding of a bf16
+    # activation the error is one bf16 ulp (2^-8 relative), once per conv
+    # layer at worst, so outputs agree to LAYERS * 2^-8 of their largest
+    # magnitude.  Adam's first update is -lr * g / (|g| + eps) ~ -lr * sign(g):
+    # a gradient that is zero up to that noise moves its weight by +lr in one
+    # run and -lr in the other, 2 * lr apart (bench default lr 3e-4) — on top
+    # of one fp32 ulp of the largest weight.
+    layers, lr = 2, 3e-4
+    again = tmp_path / "again"
+    out2 = subprocess.run(
+        [sys.executable, "bench.py", "--steps", "5", "--warmup", "1",
+         "--batch-size", "64", "--n-batches", "2", "--layers", str(layers),
+         "--hidden", "256", "--vocab", "small", "--dump-outputs", str(again)],
+        capture_output=True, text=True, timeout=540, cwd=root,
+    )
+    assert out2.returncode == 0, (out2.stdout[-2000:], out2.stderr[-2000:])
+    for n, a in arrs.items():
+        b = np.load(again / f"{n}.npy")
+        assert a.shape == b.shape, n
+        diff = float(np.abs(a.astype(np.float64) - b).max())
+        amax = float(np.abs(a).max())
+        if n == "flat_param":
+            bound = 2 * lr + amax * 2.0 ** -23
+        else:
+            bound = layers * 2.0 ** -8 * amax
+        print(f"{n}: max|a-b|={diff:.3e} max|a|={amax:.3e} bound={bound:.3e}")
+        assert diff <= bound, (n, diff, bound)
+
+
 @pytest.mark.timeout(300)
 def test_two_rank_ddp_on_one_gpu():
     world = 2

@@ -241,10 +241,15 @@ def test_cli_hipgraph_flag_cpu(tmp_path):
     import subprocess
     import sys
 
-    cmd = [sys.executable, "pert_gnn.py", "--synthetic", "--graph_type", "pert",
-           "--epochs", "2", "--num_layers", "1", "--hidden_channels", "16",
-           "--batch_size", "32", "--seed", "3", "--hipgraph",
-           "--processed_dir", str(tmp_path / "processed")]
+    argv = ["--synthetic", "--graph_type", "pert",
+            "--epochs", "2", "--num_layers", "1", "--hidden_channels", "16",
+            "--batch_size", "32", "--seed", "3", "--hipgraph",
+            "--processed_dir", str(tmp_path / "processed")]
+    # the CPU path also where a GPU is present: the CLI's main() in a fresh
+    # interpreter that reports no device
+    cmd = [sys.executable, "-c",
+           "import sys, torch; torch.cuda.is_available = lambda: False; "
+           "import pert_gnn; pert_gnn.main(sys.argv[1:])", *argv]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
                        cwd=str(Path(__file__).resolve().parents[1]))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -423,6 +428,66 @@ def test_bench_json_contract_cpu(tmp_path):
     assert rec["data"] == "synthetic"
     assert rec["config"]["global_batch"] == 16
     assert rec["value"] > 0 and rec["ms_per_step"] > 0
+    # a plain run measures the step time only: no latency-MAE probe
+    assert rec["latency_mae"] is None
+
+
+def test_bench_dump_outputs_cpu(tmp_path, monkeypatch, capsys):
+    """--dump-outputs writes the last timed step's outputs as float32 .npy
+    files, and the same arguments give the same inputs: two runs of the
+    (deterministic) CPU path agree output for output.  The dumped step starts
+    from the seeded initial state, so a run with more steps before it (ending
+    on the same batch) dumps the same arrays too."""
+    import json
+    import sys
+
+    import numpy as np
+
+    import bench as bench_mod
+
+    # the CPU path also where a GPU is present: its sums have a fixed order
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    names = ("loss", "global_predict", "local_predict", "flat_grad", "flat_param")
+    runs = []
+    for tag, steps in (("a", 2), ("b", 2), ("c", 4)):
+        out_dir = tmp_path / tag
+        monkeypatch.setattr(sys, "argv", [
+            "bench.py", "--steps", str(steps), "--warmup", "1", "--batch-size", "8",
+            "--n-batches", "2", "--layers", "2", "--hidden", "16",
+            "--vocab", "small", "--dump-outputs", str(out_dir)])
+        with torch.random.fork_rng():
+            bench_mod.main()
+        rec = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        assert rec["steps"] == steps and rec["ms_per_step"] > 0
+        assert sorted(p.name for p in out_dir.iterdir()) == sorted(f"{n}.npy" for n in names)
+        runs.append({n: np.load(out_dir / f"{n}.npy") for n in names})
+    a, b, c = runs
+    total = 0
+    for n in names:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all(), n
+        assert a[n].shape == b[n].shape and np.array_equal(a[n], b[n]), n
+        assert a[n].shape == c[n].shape and np.array_equal(a[n], c[n]), n
+        total += a[n].nbytes
+    assert total <= 64 * 1024 * 1024
+    assert a["loss"].shape == (1,) and a["global_predict"].shape == (8, 1)
+    assert np.abs(a["flat_grad"]).max() > 0, "the last step's gradients are dumped"
+
+
+def test_bench_dump_sample_is_fixed(tmp_path):
+    """An output above the per-array budget is reduced to the same seeded
+    sample of its elements in every run."""
+    import numpy as np
+
+    import bench as bench_mod
+
+    big = torch.arange(bench_mod._DUMP_MAX_ELEMS + 1000, dtype=torch.float32)
+    bench_mod.dump_outputs(str(tmp_path / "a"), {"big": big, "small": big[:7]})
+    bench_mod.dump_outputs(str(tmp_path / "b"), {"big": big})
+    a = np.load(tmp_path / "a" / "big.npy")
+    assert a.shape == (bench_mod._DUMP_MAX_ELEMS,) and a.dtype == np.float32
+    assert np.all(np.diff(a) > 0), "a sample of distinct elements, in order"
+    assert np.array_equal(a, np.load(tmp_path / "b" / "big.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), big[:7].numpy())
 
 
 def test_cli_dynamic_loss_scale_cpu(tmp_path):
