@@ -1,6 +1,12 @@
 """Microbench of the BN channel-reduction kernels at the flagship shape
 (n=180780 rows x h=256, bf16 streams) across PERTGNN_BN_BLOCKS settings.
 
+Times the three y-taking entry points, their keep-mask variants, the forward
+apply that writes the mask, and both cross-block combine candidates
+(PERTGNN_BN_COMBINE=slab|atomic).  The TB/s column is bytes actually moved
+by the call's big streams (printed next to it) over the wall time of the
+whole entry point, small fold/finalize launches included.
+
 Run (GPU box): for B in 512 1024 2048 2825; do
   PERTGNN_BN_BLOCKS=$B PYTHONPATH=. python benchmarks/bn_micro.py; done
 """
@@ -21,6 +27,11 @@ def timeit(fn, iters=200):
     return (time.perf_counter() - t0) / iters * 1e6
 
 
+def line(name, us, nbytes):
+    print(f"  {name:<34} {us:7.1f} us  {nbytes / 1e6:6.1f} MB  "
+          f"{nbytes / us / 1e6:4.1f} TB/s")
+
+
 def main():
     import pertgnn._C as C
 
@@ -28,21 +39,50 @@ def main():
     n, h = 180780, 256
     x = torch.randn(n, h, device=dev).to(torch.bfloat16)
     g = torch.randn(n, h, device=dev).to(torch.bfloat16)
-    y = torch.relu(torch.randn(n, h, device=dev)).to(torch.bfloat16)
-    mean = torch.zeros(h, device=dev)
-    invstd = torch.ones(h, device=dev)
-
-    t_stats = timeit(lambda: C.bn_stats(x))
-    t_bwd = timeit(lambda: C.bn_bwd_partials16(g, x, y, mean, invstd, True, 1.0))
     gamma = torch.ones(h, device=dev)
-    part = C.bn_bwd_partials16(g, x, y, mean, invstd, True, 1.0)
-    t_apply = timeit(lambda: C.bn_bwd_apply16(g, x, y, mean, invstd, gamma,
-                                              part, part, True, 1.0))
-    gb = n * h * 2 / 1e9
+    beta = torch.zeros(h, device=dev)
+    rm = torch.zeros(h, device=dev)
+    rv = torch.ones(h, device=dev)
+    seed = torch.empty(0, dtype=torch.int64, device=dev)
+    out = C.bn_relu_fwd16(x, gamma, beta, rm, rv, 0.1, 1e-5, True, True, 0.0,
+                          seed)
+    y, mean, invstd = out[:3]
+    mask = out[3] if len(out) > 3 and out[3].numel() else None
+
+    s = n * h * 2  # one bf16 stream
+    mb = n * h // 8  # the bit-packed mask
     blocks = os.environ.get("PERTGNN_BN_BLOCKS", "512(default)")
-    print(f"blocks={blocks:>14}  bn_stats {t_stats:7.1f} us ({gb / t_stats * 1e6 / 1e3:4.1f} TB/s)"
-          f"  bn_bwd_partials {t_bwd:7.1f} us ({3 * gb / t_bwd * 1e6 / 1e3:4.1f} TB/s)"
-          f"  bn_bwd_apply {t_apply:7.1f} us ({4 * gb / t_apply * 1e6 / 1e3:4.1f} TB/s)")
+    for combine in ("slab", "atomic"):
+        os.environ["PERTGNN_BN_COMBINE"] = combine
+        print(f"blocks={blocks} combine={combine}")
+        line("bn_stats", timeit(lambda: C.bn_stats(x)), s)
+        line("bn_bwd_partials16 (y)", timeit(
+            lambda: C.bn_bwd_partials16(g, x, y, mean, invstd, True, 1.0)),
+            3 * s)
+        part = C.bn_bwd_partials16(g, x, y, mean, invstd, True, 1.0)
+        if mask is not None:
+            line("bn_bwd_partials16 (mask)", timeit(
+                lambda: C.bn_bwd_partials16(g, x, mask, mean, invstd, True,
+                                            1.0)), 2 * s + mb)
+            line("bn_relu_bwd16 (mask, whole bwd)", timeit(
+                lambda: C.bn_relu_bwd16(g, x, gamma, mean, invstd, mask, True,
+                                        1.0)), 5 * s + 2 * mb)
+        line("bn_relu_bwd16 (y, whole bwd)", timeit(
+            lambda: C.bn_relu_bwd16(g, x, gamma, mean, invstd, y, True, 1.0)),
+            7 * s)
+        line("bn_relu_fwd16 (whole fwd)", timeit(
+            lambda: C.bn_relu_fwd16(x, gamma, beta, rm, rv, 0.1, 1e-5, True,
+                                    True, 0.0, seed)),
+            3 * s + (mb if mask is not None else 0))
+    os.environ.pop("PERTGNN_BN_COMBINE")
+    # the apply kernels do not depend on the combine
+    line("bn_bwd_apply16 (y)", timeit(
+        lambda: C.bn_bwd_apply16(g, x, y, mean, invstd, gamma, part, part,
+                                 True, 1.0)), 4 * s)
+    if mask is not None:
+        line("bn_bwd_apply16 (mask)", timeit(
+            lambda: C.bn_bwd_apply16(g, x, mask, mean, invstd, gamma, part,
+                                     part, True, 1.0)), 3 * s + mb)
 
     # parity across block counts (vs plain torch fp32 on rounded operands)
     p = C.bn_stats(x)

@@ -41,14 +41,21 @@ void launch_embed_edge_fwd(const long*, const float*, const float*, float*,
                            long, int, int, hipStream_t);
 void launch_gather_rows(const long*, const float*, float*, long, int,
                         hipStream_t);
+// wide-load BN path: fast-path shape test, and the per-call slab rows a
+// reduction over [n, h] needs (0 = none); trailing float* = that slab,
+// trailing unsigned char* = bit-packed ReLU keep mask [n, h/8] (or null)
+bool bn_wide_ok(int);
+int bn_wide_slab_rows(long, int);
 void launch_bn_fwd(const float*, const float*, const float*, float*, float*,
                    float*, float*, float*, float*, long, int, float, float,
-                   bool, bool, float, const unsigned long long*, hipStream_t);
+                   bool, bool, float, const unsigned long long*, float*,
+                   hipStream_t);
 void launch_counter_bump(unsigned long long*, hipStream_t);
 void launch_bn_bwd(const float*, const float*, const float*, const float*,
                    const float*, const float*, float*, float*, float*, float*,
-                   long, int, bool, float, hipStream_t);
-void launch_bn_stats_only(const float*, long, int, float*, hipStream_t);
+                   long, int, bool, float, float*, hipStream_t);
+void launch_bn_stats_only(const float*, long, int, float*, float*,
+                          hipStream_t);
 void launch_bn_finalize_apply(const float*, const float*, const float*,
                               const float*, const float*, float*, float*,
                               float*, float*, float*, long, int, float, float,
@@ -56,33 +63,37 @@ void launch_bn_finalize_apply(const float*, const float*, const float*,
                               hipStream_t);
 void launch_bn_bwd_partials_only(const float*, const float*, const float*,
                                  const float*, const float*, long, int, bool,
-                                 float*, float, hipStream_t);
+                                 float*, float, float*, hipStream_t);
 void launch_bn_bwd_apply_only(const float*, const float*, const float*,
                               const float*, const float*, const float*,
                               const float*, const float*, float*, long, int,
                               bool, float, hipStream_t);
 void launch_bn_grad_affine(const float*, float*, float*, int, hipStream_t);
 // act16 variants (bf16 x/y/g/dx streams, fp32 statistics)
-void launch_bn_stats_only16(const void*, long, int, float*, hipStream_t);
+void launch_bn_stats_only16(const void*, long, int, float*, float*,
+                            hipStream_t);
 void launch_bn_fwd16(const void*, const float*, const float*, float*, float*,
                      float*, float*, float*, void*, long, int, float, float,
-                     bool, bool, float, const unsigned long long*,
-                     hipStream_t);
+                     bool, bool, float, const unsigned long long*, float*,
+                     unsigned char*, hipStream_t);
 void launch_bn_finalize_apply16(const void*, const float*, const float*,
                                 const float*, const float*, float*, float*,
                                 float*, float*, void*, long, int, float, float,
                                 bool, bool, float, const unsigned long long*,
-                                hipStream_t);
+                                unsigned char*, hipStream_t);
 void launch_bn_bwd_partials_only16(const void*, const void*, const void*,
                                    const float*, const float*, long, int, bool,
-                                   float*, float, hipStream_t);
+                                   float*, float, float*,
+                                   const unsigned char*, hipStream_t);
 void launch_bn_bwd_apply_only16(const void*, const void*, const void*,
                                 const float*, const float*, const float*,
                                 const float*, const float*, void*, long, int,
-                                bool, float, hipStream_t);
+                                bool, float, const unsigned char*,
+                                hipStream_t);
 void launch_bn_bwd16(const void*, const void*, const void*, const float*,
                      const float*, const float*, float*, void*, float*,
-                     float*, long, int, bool, float, hipStream_t);
+                     float*, long, int, bool, float, float*,
+                     const unsigned char*, hipStream_t);
 void launch_seg_pool_fwd16(const void*, const float*, const float*,
                            const int*, float*, float*, int, int, int,
                            hipStream_t);
@@ -320,6 +331,38 @@ static const unsigned long long* rng_seed_ptr(torch::Tensor& seed,
   return (const unsigned long long*)seed.data_ptr<long>();
 }
 
+// Per-call slab of the wide BN reductions (one [2h] row per block, folded in
+// fixed order).  Caching-allocator memory is stream-ordered, so this is safe
+// under hipGraph capture and when BN calls overlap on a side stream.
+static torch::Tensor bn_wide_slab(const torch::Tensor& x) {
+  const long rows = bn_wide_slab_rows(x.size(0), (int)x.size(1));
+  return torch::empty({rows, 2 * x.size(1)},
+                      x.options().dtype(torch::kFloat32));
+}
+static float* bn_slab_ptr(const torch::Tensor& slab) {
+  return slab.numel() ? slab.data_ptr<float>() : nullptr;
+}
+// y-or-mask argument of the act16 backward entry points: a uint8 tensor is
+// the bit-packed keep mask [n, h/8] of the forward, anything else is y
+static const unsigned char* bn_mask_ptr(const torch::Tensor& ym,
+                                        const torch::Tensor& x) {
+  if (ym.scalar_type() != torch::kUInt8) return nullptr;
+  TORCH_CHECK(ym.is_contiguous() && x.size(1) % 8 == 0 &&
+                  ym.numel() == x.size(0) * (x.size(1) / 8) &&
+                  bn_wide_ok((int)x.size(1)),
+              "BN keep mask must be a contiguous uint8 [n, h/8] tensor");
+  return ym.data_ptr<unsigned char>();
+}
+// keep mask written by a training forward with ReLU on a fast-path shape
+// (empty tensor otherwise: eval mode, relu=false and other shapes write none)
+static torch::Tensor bn_new_mask(const torch::Tensor& x, bool training,
+                                 bool relu) {
+  const long n = x.size(0), h = x.size(1);
+  const bool on = training && relu && n > 0 && bn_wide_ok((int)h);
+  return torch::empty({on ? n : 0, on ? h / 8 : 0},
+                      x.options().dtype(torch::kUInt8));
+}
+
 std::vector<torch::Tensor> bn_relu_fwd(torch::Tensor x, torch::Tensor gamma,
                                        torch::Tensor beta,
                                        torch::Tensor running_mean,
@@ -335,13 +378,15 @@ std::vector<torch::Tensor> bn_relu_fwd(torch::Tensor x, torch::Tensor gamma,
   auto mean = torch::empty({h}, x.options());
   auto invstd = torch::empty({h}, x.options());
   auto partials = torch::empty({2 * h}, x.options());
+  auto slab = training ? bn_wide_slab(x) : torch::empty({0}, x.options());
   const auto* sp = rng_seed_ptr(seed, dropout_p);
   launch_bn_fwd(x.data_ptr<float>(), gamma.data_ptr<float>(),
                 beta.data_ptr<float>(), running_mean.data_ptr<float>(),
                 running_var.data_ptr<float>(), mean.data_ptr<float>(),
                 invstd.data_ptr<float>(), partials.data_ptr<float>(),
                 y.data_ptr<float>(), n, h, (float)momentum, (float)eps,
-                training, relu, (float)dropout_p, sp, cur_stream());
+                training, relu, (float)dropout_p, sp, bn_slab_ptr(slab),
+                cur_stream());
   if (sp) launch_counter_bump((unsigned long long*)seed.data_ptr<long>(),
                               cur_stream());
   return {y, mean, invstd};
@@ -358,12 +403,13 @@ std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor g, torch::Tensor x,
   auto dgamma = torch::empty({h}, x.options());
   auto dbeta = torch::empty({h}, x.options());
   auto partials = torch::empty({2 * h}, x.options());
+  auto slab = bn_wide_slab(x);
   launch_bn_bwd(g.data_ptr<float>(), x.data_ptr<float>(), y.data_ptr<float>(),
                 mean.data_ptr<float>(), invstd.data_ptr<float>(),
                 gamma.data_ptr<float>(), partials.data_ptr<float>(),
                 dx.data_ptr<float>(), dgamma.data_ptr<float>(),
                 dbeta.data_ptr<float>(), n, h, relu, (float)keep_inv,
-                cur_stream());
+                bn_slab_ptr(slab), cur_stream());
   return {dx, dgamma, dbeta};
 }
 
@@ -755,12 +801,15 @@ torch::Tensor bn_stats(torch::Tensor x) {
   const long h = x.size(1);
   auto partials = torch::empty({2 * h + 1},
                                x.options().dtype(torch::kFloat32));
+  auto slab = bn_wide_slab(x);
   if (x.scalar_type() == torch::kBFloat16)
     launch_bn_stats_only16(x.data_ptr(), x.size(0), h,
-                           partials.data_ptr<float>(), cur_stream());
+                           partials.data_ptr<float>(), bn_slab_ptr(slab),
+                           cur_stream());
   else
     launch_bn_stats_only(x.data_ptr<float>(), x.size(0), h,
-                         partials.data_ptr<float>(), cur_stream());
+                         partials.data_ptr<float>(), bn_slab_ptr(slab),
+                         cur_stream());
   partials.narrow(0, 2 * h, 1).fill_((float)x.size(0));
   return partials;
 }
@@ -799,11 +848,13 @@ torch::Tensor bn_bwd_partials(torch::Tensor g, torch::Tensor x,
   CHECK_IN(g); CHECK_IN(x);
   const long h = x.size(1);
   auto partials = torch::empty({2 * h + 1}, x.options());
+  auto slab = bn_wide_slab(x);
   launch_bn_bwd_partials_only(g.data_ptr<float>(), x.data_ptr<float>(),
                               y.data_ptr<float>(), mean.data_ptr<float>(),
                               invstd.data_ptr<float>(), x.size(0), h,
                               relu, partials.data_ptr<float>(),
-                              (float)keep_inv, cur_stream());
+                              (float)keep_inv, bn_slab_ptr(slab),
+                              cur_stream());
   partials.narrow(0, 2 * h, 1).fill_((float)x.size(0));
   return partials;
 }
@@ -979,16 +1030,20 @@ std::vector<torch::Tensor> bn_relu_fwd16(torch::Tensor x, torch::Tensor gamma,
   auto mean = torch::empty({h}, fopt);
   auto invstd = torch::empty({h}, fopt);
   auto partials = torch::empty({2 * h}, fopt);
+  auto slab = training ? bn_wide_slab(x) : torch::empty({0}, fopt);
+  auto mask = bn_new_mask(x, training, relu);
   const auto* sp = rng_seed_ptr(seed, dropout_p);
   launch_bn_fwd16(x.data_ptr(), gamma.data_ptr<float>(),
                   beta.data_ptr<float>(), running_mean.data_ptr<float>(),
                   running_var.data_ptr<float>(), mean.data_ptr<float>(),
                   invstd.data_ptr<float>(), partials.data_ptr<float>(),
                   y.data_ptr(), n, h, (float)momentum, (float)eps, training,
-                  relu, (float)dropout_p, sp, cur_stream());
+                  relu, (float)dropout_p, sp, bn_slab_ptr(slab),
+                  mask.numel() ? mask.data_ptr<unsigned char>() : nullptr,
+                  cur_stream());
   if (sp) launch_counter_bump((unsigned long long*)seed.data_ptr<long>(),
                               cur_stream());
-  return {y, mean, invstd};
+  return {y, mean, invstd, mask};
 }
 
 std::vector<torch::Tensor> bn_relu_bwd16(torch::Tensor g, torch::Tensor x,
@@ -1004,12 +1059,13 @@ std::vector<torch::Tensor> bn_relu_bwd16(torch::Tensor g, torch::Tensor x,
   auto dgamma = torch::empty({h}, fopt);
   auto dbeta = torch::empty({h}, fopt);
   auto partials = torch::empty({2 * h}, fopt);
+  auto slab = bn_wide_slab(x);
   launch_bn_bwd16(g.data_ptr(), x.data_ptr(), y.data_ptr(),
                   mean.data_ptr<float>(), invstd.data_ptr<float>(),
                   gamma.data_ptr<float>(), partials.data_ptr<float>(),
                   dx.data_ptr(), dgamma.data_ptr<float>(),
                   dbeta.data_ptr<float>(), n, h, relu, (float)keep_inv,
-                  cur_stream());
+                  bn_slab_ptr(slab), bn_mask_ptr(y, x), cur_stream());
   return {dx, dgamma, dbeta};
 }
 
@@ -1027,6 +1083,7 @@ std::vector<torch::Tensor> bn_finalize_apply16(
   auto y = torch::empty({x.size(0), h}, x.options().dtype(torch::kBFloat16));
   auto mean = torch::empty({h}, fopt);
   auto invstd = torch::empty({h}, fopt);
+  auto mask = bn_new_mask(x, training, relu);
   const auto* sp = rng_seed_ptr(seed, dropout_p);
   launch_bn_finalize_apply16(
       x.data_ptr(), partials.data_ptr<float>(),
@@ -1035,10 +1092,11 @@ std::vector<torch::Tensor> bn_finalize_apply16(
       running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
       mean.data_ptr<float>(), invstd.data_ptr<float>(), y.data_ptr(),
       x.size(0), h, (float)momentum, (float)eps, training, relu,
-      (float)dropout_p, sp, cur_stream());
+      (float)dropout_p, sp,
+      mask.numel() ? mask.data_ptr<unsigned char>() : nullptr, cur_stream());
   if (sp) launch_counter_bump((unsigned long long*)seed.data_ptr<long>(),
                               cur_stream());
-  return {y, mean, invstd};
+  return {y, mean, invstd, mask};
 }
 
 torch::Tensor bn_bwd_partials16(torch::Tensor g, torch::Tensor x,
@@ -1049,11 +1107,13 @@ torch::Tensor bn_bwd_partials16(torch::Tensor g, torch::Tensor x,
   const long h = x.size(1);
   auto partials = torch::empty({2 * h + 1},
                                x.options().dtype(torch::kFloat32));
+  auto slab = bn_wide_slab(x);
   launch_bn_bwd_partials_only16(g.data_ptr(), x.data_ptr(),
                                 y.data_ptr(), mean.data_ptr<float>(),
                                 invstd.data_ptr<float>(), x.size(0), h,
                                 relu, partials.data_ptr<float>(),
-                                (float)keep_inv, cur_stream());
+                                (float)keep_inv, bn_slab_ptr(slab),
+                                bn_mask_ptr(y, x), cur_stream());
   partials.narrow(0, 2 * h, 1).fill_((float)x.size(0));
   return partials;
 }
@@ -1077,7 +1137,7 @@ std::vector<torch::Tensor> bn_bwd_apply16(
                              partials_global.data_ptr<float>(),
                              partials_global.data_ptr<float>() + 2 * h,
                              dx.data_ptr(), x.size(0), h, relu,
-                             (float)keep_inv, cur_stream());
+                             (float)keep_inv, bn_mask_ptr(y, x), cur_stream());
   launch_bn_grad_affine(partials_local.data_ptr<float>(),
                         dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), h,
                         cur_stream());

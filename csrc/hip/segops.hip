@@ -1006,9 +1006,11 @@ __global__ void bn_slab_reduce_kernel(const float* __restrict__ slab, int nb,
   out[c] = s;
 }
 
-// lazily-allocated device slab for the deterministic BN reductions
-// (512 blocks x 2 x 1024 channels); deterministic mode is documented as
-// incompatible with hipGraph capture, so the lazy hipMalloc is safe.
+// lazily-allocated device slab for the deterministic BN reductions of the
+// pair-per-thread kernels (512 blocks x 2 x 1024 channels); deterministic
+// mode is documented as incompatible with hipGraph capture, so the lazy
+// hipMalloc is safe.  The wide-load path below does not use it: its slab is
+// a per-call tensor from the binding layer.
 static float* bn_det_slab() {
   static float* p = [] {
     float* q = nullptr;
@@ -1335,6 +1337,467 @@ __global__ void bn_grad_affine_kernel(const float* __restrict__ partials,
   dbeta[c] = partials[c];
 }
 
+// ---------------------------------------------------------------------------
+// Wide-load BN reductions: every lane owns 8 ADJACENT channels and loads them
+// with one 16-B instruction (two for an fp32 stream); h/8 lanes cover a row
+// and a 256-thread block covers 256/(h/8) rows ("row slots") per iteration.
+// Taken when h % 8 == 0 and 256 % (h/8) == 0 (h = 8..2048 in powers of
+// two); every other shape stays on the pair-per-thread kernels above.
+//
+// The bf16 training forward with ReLU also emits a bit-packed keep mask
+// mask[N, h/8] (bit u of byte (r, c/8) = !(y[r, c+u] <= 0) on the STORED
+// bf16 value, after dropout), and the backward reads that 1 bit/element in
+// place of the whole y stream.
+// ---------------------------------------------------------------------------
+
+bool bn_wide_ok(int h) {
+  return h >= 8 && (h & 7) == 0 && 256 % (h >> 3) == 0;
+}
+
+// cross-block combine of the wide reductions: per-block slab row + fixed-
+// order fold kernel (default, also the deterministic mode), or float atomics
+// into the one partials row (PERTGNN_BN_COMBINE=atomic)
+static inline bool bn_wide_atomic() {
+  if (pertgnn_deterministic_seg()) return false;
+  const char* e = getenv("PERTGNN_BN_COMBINE");
+  return e && e[0] == 'a';
+}
+
+// grid of the wide reductions.  PERTGNN_BN_BLOCKS is taken as given (blocks
+// with an empty row range contribute exact zeros), clamped to 4096.
+static inline int bn_wide_blocks(long n) {
+  const char* e = getenv("PERTGNN_BN_BLOCKS");
+  const int env = e ? atoi(e) : 0;
+  if (env > 0) return env < 4096 ? env : 4096;
+  const long cap = (n + 63) / 64;
+  return (int)(cap < 512 ? (cap > 0 ? cap : 1) : 512);
+}
+
+// slab rows ([rows, 2h] fp32) the caller has to provide for a wide reduction
+// over [n, h]; 0 = no slab (other shape, n == 0, or the atomic combine)
+int bn_wide_slab_rows(long n, int h) {
+  if (n <= 0 || !bn_wide_ok(h) || bn_wide_atomic()) return 0;
+  return bn_wide_blocks(n);
+}
+
+typedef __attribute__((ext_vector_type(4))) unsigned int bn_u4;
+
+// 8 adjacent bf16 -> fp32 from one 16-B load (bf16 -> fp32 is a 16-bit shift)
+__device__ __forceinline__ void bn_ld8(const __bf16* p, float (&v)[8]) {
+  const bn_u4 w = *reinterpret_cast<const bn_u4*>(p);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    v[2 * k] = __uint_as_float(w[k] << 16);
+    v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
+  }
+}
+
+// fp32 stream: the lane's 8 channels are two 16-B loads
+__device__ __forceinline__ void bn_ld8(const float* p, float (&v)[8]) {
+  typedef __attribute__((ext_vector_type(4))) float bn_f4;
+  const bn_f4 a = *reinterpret_cast<const bn_f4*>(p);
+  const bn_f4 b = *reinterpret_cast<const bn_f4*>(p + 4);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    v[k] = a[k];
+    v[4 + k] = b[k];
+  }
+}
+
+__device__ __forceinline__ void bn_st8(__bf16* p, const __bf16 (&o)[8]) {
+  bn_u4 w;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    w[k] = (unsigned)__builtin_bit_cast(unsigned short, o[2 * k]) |
+           ((unsigned)__builtin_bit_cast(unsigned short, o[2 * k + 1]) << 16);
+  *reinterpret_cast<bn_u4*>(p) = w;
+}
+
+// end of a wide reduction block: fold the row slots through LDS in slot
+// order, then one value per (block, column): slab row store or atomic.
+// red holds slots x 2h = 4096 floats for every fast-path h.
+__device__ __forceinline__ void bn_wide_combine(
+    float* __restrict__ red, const float (&s)[8], const float (&q)[8],
+    int slot, int slots, int c0, int h, float* __restrict__ out, int slab,
+    bool nonempty) {
+  const int w = 2 * h;
+  float* row = red + slot * w;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    row[c0 + j] = s[j];
+    row[h + c0 + j] = q[j];
+  }
+  __syncthreads();
+  for (int col = threadIdx.x; col < w; col += 256) {
+    float a = 0.f;
+    for (int sl = 0; sl < slots; ++sl) a += red[sl * w + col];
+    if (slab)
+      out[(long)blockIdx.x * w + col] = a;
+    else if (nonempty)
+      atomicAdd(&out[col], a);
+  }
+}
+
+// forward statistics.  U row groups are unrolled so that a lane has 128 B of
+// loads in flight (U = 8 for bf16, 4 for fp32): 8 KiB per wave, 32 KiB per
+// block.  kernel-resource-usage: 122 VGPRs (bf16; 68 fp32), 16 KiB LDS, no
+// scratch -> occupancy 4 (7) waves/SIMD, so both blocks/CU of the default
+// 512-block grid are resident and keep ~64 KiB of loads in flight per CU.
+template <typename TS, int U>
+__global__ __launch_bounds__(256) void bn_stats_wide_kernel(
+    const TS* __restrict__ x, long n, int h, float* __restrict__ out,
+    int slab) {
+  __shared__ float red[4096];
+  const int lpr = h >> 3;  // lanes per row
+  const int slots = 256 / lpr;
+  const int slot = threadIdx.x / lpr;
+  const int c0 = (threadIdx.x - slot * lpr) * 8;
+  const long rows_per_block = (n + gridDim.x - 1) / gridDim.x;
+  const long r0 = (long)blockIdx.x * rows_per_block;
+  const long r1 = min(n, r0 + rows_per_block);
+  float s[8], q[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
+  long r = r0 + slot;
+  for (; r + (long)(U - 1) * slots < r1; r += (long)U * slots) {
+    float v[U][8];
+#pragma unroll
+    for (int u = 0; u < U; ++u) bn_ld8(&x[(r + (long)u * slots) * h + c0], v[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        s[j] += v[u][j];
+        q[j] += v[u][j] * v[u][j];
+      }
+  }
+  for (; r < r1; r += slots) {
+    float v[8];
+    bn_ld8(&x[r * h + c0], v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      s[j] += v[j];
+      q[j] += v[j] * v[j];
+    }
+  }
+  bn_wide_combine(red, s, q, slot, slots, c0, h, out, slab, r0 < r1);
+}
+
+// backward partials.  MODE 0: no ReLU (neither y nor the mask is touched),
+// 1: ReLU from y, 2: ReLU from the bit-packed mask.  U = 4 row groups for
+// bf16 (2 for fp32): (g + x [+ y]) x 64 B per lane = 8-12 KiB per wave,
+// 32-48 KiB per block.  kernel-resource-usage: 124 VGPRs without ReLU, 166
+// with y or mask (bf16; 82-96 fp32), 16 KiB LDS, no scratch -> occupancy
+// 4 / 3 (5) waves/SIMD, so both blocks/CU of the 512-block grid are resident
+// and keep 64+ KiB of loads in flight per CU.
+template <typename TS, int MODE, int U>
+__global__ __launch_bounds__(256) void bn_bwd_partial_wide_kernel(
+    const TS* __restrict__ g, const TS* __restrict__ x,
+    const void* __restrict__ ym, const float* __restrict__ mean,
+    const float* __restrict__ invstd, long n, int h, float* __restrict__ out,
+    int slab, float keep_inv) {
+  __shared__ float red[4096];
+  const TS* y = (const TS*)ym;
+  const unsigned char* mask = (const unsigned char*)ym;
+  const int lpr = h >> 3;
+  const int slots = 256 / lpr;
+  const int slot = threadIdx.x / lpr;
+  const int lane = threadIdx.x - slot * lpr;
+  const int c0 = lane * 8;
+  const long rows_per_block = (n + gridDim.x - 1) / gridDim.x;
+  const long r0 = (long)blockIdx.x * rows_per_block;
+  const long r1 = min(n, r0 + rows_per_block);
+  float s[8], q[8], m[8], is[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    s[j] = q[j] = 0.f;
+    m[j] = mean[c0 + j];
+    is[j] = invstd[c0 + j];
+  }
+  auto acc = [&](const float (&gv)[8], const float (&xv)[8],
+                 const float (&yv)[8], unsigned bits) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      bool dead = false;
+      if (MODE == 1) dead = yv[j] <= 0.f;
+      if (MODE == 2) dead = !((bits >> j) & 1u);
+      const float gm = dead ? 0.f : gv[j] * keep_inv;
+      s[j] += gm;
+      q[j] += gm * (xv[j] - m[j]) * is[j];
+    }
+  };
+  long r = r0 + slot;
+  for (; r + (long)(U - 1) * slots < r1; r += (long)U * slots) {
+    float gv[U][8], xv[U][8], yv[U][8];
+    unsigned bits[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long rr = r + (long)u * slots;
+      bn_ld8(&g[rr * h + c0], gv[u]);
+      bn_ld8(&x[rr * h + c0], xv[u]);
+      if (MODE == 1) bn_ld8(&y[rr * h + c0], yv[u]);
+      bits[u] = (MODE == 2) ? mask[rr * lpr + lane] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc(gv[u], xv[u], yv[u], bits[u]);
+  }
+  for (; r < r1; r += slots) {
+    float gv[8], xv[8], yv[8];
+    bn_ld8(&g[r * h + c0], gv);
+    bn_ld8(&x[r * h + c0], xv);
+    if (MODE == 1) bn_ld8(&y[r * h + c0], yv);
+    const unsigned bits = (MODE == 2) ? mask[r * lpr + lane] : 0u;
+    acc(gv, xv, yv, bits);
+  }
+  bn_wide_combine(red, s, q, slot, slots, c0, h, out, slab, r0 < r1);
+}
+
+__device__ __forceinline__ void bn_finalize_one(
+    int c, float sum, float sumsq, float nf, float eps, float momentum,
+    float* __restrict__ mean, float* __restrict__ invstd,
+    float* __restrict__ running_mean, float* __restrict__ running_var) {
+  // same math as bn_finalize_kernel (training: running stats always updated)
+  const float m = sum / nf;
+  const float var = fmaxf(sumsq / nf - m * m, 0.f);
+  mean[c] = m;
+  invstd[c] = rsqrtf(var + eps);
+  const float unbiased = (nf > 1.f) ? var * nf / (nf - 1.f) : var;
+  running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+  running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+}
+
+// fixed-order fold of the slab rows of a wide reduction into partials[2h],
+// with the per-channel epilogue of its direction fused in (no extra launch,
+// no memset): EPI 1 = bn_finalize math, EPI 2 = dgamma/dbeta copy.
+// Block = 8 channels x {sum, sumsq} x 16 row slices; slices are folded in
+// slice order, rows inside a slice in row order.
+template <int EPI>
+__global__ __launch_bounds__(256) void bn_slab_fold_kernel(
+    const float* __restrict__ slab, int nb, int h,
+    float* __restrict__ partials, long n, float eps, float momentum,
+    float* __restrict__ o0, float* __restrict__ o1,
+    float* __restrict__ running_mean, float* __restrict__ running_var) {
+  __shared__ float red[16][16];
+  __shared__ float tot[16];
+  const int j = threadIdx.x & 15;
+  const int sl = threadIdx.x >> 4;
+  const int ch = blockIdx.x * 8 + (j & 7);
+  const int col = (j >> 3) * h + ch;
+  const int per = (nb + 15) / 16;
+  const int b0 = sl * per;
+  const int b1 = min(nb, b0 + per);
+  float a = 0.f;
+  if (ch < h) {
+#pragma unroll 8
+    for (int b = b0; b < b1; ++b) a += slab[(long)b * 2 * h + col];
+  }
+  red[sl][j] = a;
+  __syncthreads();
+  if (threadIdx.x < 16) {
+    float t = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t += red[k][threadIdx.x];
+    tot[threadIdx.x] = t;
+    if (ch < h) partials[col] = t;
+  }
+  if (EPI == 0) return;
+  __syncthreads();
+  if (threadIdx.x < 8 && ch < h) {
+    if (EPI == 1) {
+      bn_finalize_one(ch, tot[threadIdx.x], tot[8 + threadIdx.x], (float)n,
+                      eps, momentum, o0, o1, running_mean, running_var);
+    } else {
+      o0[ch] = tot[8 + threadIdx.x];  // dgamma = sum gm*xhat
+      o1[ch] = tot[threadIdx.x];      // dbeta = sum gm
+    }
+  }
+}
+
+// wide forward statistics into partials[2h]; finalize != 0 also writes
+// mean/invstd and updates the running stats (fused path, local count n).
+// slab == nullptr selects the atomic combine.
+template <typename TS>
+static void bn_stats_wide_launch(const TS* x, long n, int h,
+                                 float* partials, float* slab, bool finalize,
+                                 float eps, float momentum, float* mean,
+                                 float* invstd, float* running_mean,
+                                 float* running_var, hipStream_t s) {
+  const int nb = bn_wide_blocks(n);
+  constexpr int U = 16 / sizeof(TS);
+  if (slab) {
+    bn_stats_wide_kernel<TS, U><<<nb, 256, 0, s>>>(x, n, h, slab, 1);
+    if (finalize)
+      bn_slab_fold_kernel<1><<<h / 8, 256, 0, s>>>(
+          slab, nb, h, partials, n, eps, momentum, mean, invstd, running_mean,
+          running_var);
+    else
+      bn_slab_fold_kernel<0><<<h / 8, 256, 0, s>>>(
+          slab, nb, h, partials, n, 0.f, 0.f, nullptr, nullptr, nullptr,
+          nullptr);
+    return;
+  }
+  HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
+  bn_stats_wide_kernel<TS, U><<<nb, 256, 0, s>>>(x, n, h, partials, 0);
+  if (finalize)
+    bn_finalize_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+        partials, n, h, eps, momentum, mean, invstd, running_mean,
+        running_var, 1);
+}
+
+// wide backward partials into partials[2h]; dgamma != nullptr also writes
+// dgamma/dbeta.  mask (uint8 [n, h/8]) takes precedence over y.
+template <typename TS>
+static void bn_bwd_partials_wide_launch(
+    const TS* g, const TS* x, const TS* y,
+    const unsigned char* mask, const float* mean, const float* invstd, long n,
+    int h, bool relu, float* partials, float* slab, float* dgamma,
+    float* dbeta, float keep_inv, hipStream_t s) {
+  const int nb = bn_wide_blocks(n);
+  float* out = slab ? slab : partials;
+  const int sl = slab ? 1 : 0;
+  constexpr int U = 8 / sizeof(TS);
+  if (!slab) HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
+  if (!relu)
+    bn_bwd_partial_wide_kernel<TS, 0, U><<<nb, 256, 0, s>>>(
+        g, x, nullptr, mean, invstd, n, h, out, sl, keep_inv);
+  else if (mask)
+    bn_bwd_partial_wide_kernel<TS, 2, U><<<nb, 256, 0, s>>>(
+        g, x, mask, mean, invstd, n, h, out, sl, keep_inv);
+  else
+    bn_bwd_partial_wide_kernel<TS, 1, U><<<nb, 256, 0, s>>>(
+        g, x, y, mean, invstd, n, h, out, sl, keep_inv);
+  if (slab) {
+    if (dgamma)
+      bn_slab_fold_kernel<2><<<h / 8, 256, 0, s>>>(
+          slab, nb, h, partials, n, 0.f, 0.f, dgamma, dbeta, nullptr,
+          nullptr);
+    else
+      bn_slab_fold_kernel<0><<<h / 8, 256, 0, s>>>(
+          slab, nb, h, partials, n, 0.f, 0.f, nullptr, nullptr, nullptr,
+          nullptr);
+  } else if (dgamma) {
+    bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(partials, dgamma,
+                                                           dbeta, h);
+  }
+}
+
+// 8-wide training apply with ReLU for the fast-path shapes: one 16-B bf16
+// load, one 16-B store and one mask byte per thread and step.  h divides
+// 2048 = 8 x blockDim, so a thread keeps the same 8 channels over the whole
+// grid-stride loop and the per-channel parameters stay in registers.
+// DROP stays a template parameter (see bn_apply_kernel).
+template <bool DROP>
+__global__ __launch_bounds__(256) void bn_apply_mask_kernel(
+    const __bf16* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ gamma,
+    const float* __restrict__ beta, __bf16* __restrict__ y,
+    unsigned char* __restrict__ mask, long n, int h, float dropout_p,
+    const unsigned long long* __restrict__ seed_ptr) {
+  const float keep_inv = DROP ? 1.f / (1.f - dropout_p) : 1.f;
+  unsigned long long seed = 0ull;
+  if constexpr (DROP) seed = seed_ptr ? *seed_ptr : 0ull;
+  const long numo = n * (h >> 3);
+  const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const int c = (int)((i0 * 8) % h);
+  float mu[8], is[8], ga[8], be[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    mu[u] = mean[c + u];
+    is[u] = invstd[c + u];
+    ga[u] = gamma[c + u];
+    be[u] = beta[c + u];
+  }
+  for (long o = i0; o < numo; o += stride) {
+    const long t = o * 8;
+    float xv[8];
+    bn_ld8(&x[t], xv);
+    __bf16 ov[8];
+    unsigned bits = 0u;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      float v = (xv[u] - mu[u]) * is[u] * ga[u] + be[u];
+      v = fmaxf(v, 0.f);
+      if constexpr (DROP)
+        v = (bn_rand01(seed, t + u) >= dropout_p) ? v * keep_inv : 0.f;
+      ov[u] = (__bf16)v;
+      // the backward's `y <= 0` test on the stored value, NaNs included
+      if (!((float)ov[u] <= 0.f)) bits |= 1u << u;
+    }
+    bn_st8(&y[t], ov);
+    mask[o] = (unsigned char)bits;
+  }
+}
+
+// 8-wide backward apply with ReLU for the fast-path shapes (same thread ->
+// channel invariance as bn_apply_mask_kernel).  MODE 2 reads the keep mask
+// (1 B per 8 elements) instead of y; MODE 1 reads bf16 y, so the two give
+// bitwise-equal dx.
+template <int MODE>
+__global__ __launch_bounds__(256) void bn_bwd_apply_wide_kernel(
+    const __bf16* __restrict__ g, const __bf16* __restrict__ x,
+    const void* __restrict__ ym, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ gamma,
+    const float* __restrict__ partials, __bf16* __restrict__ dx, long n,
+    long count, int h, const float* __restrict__ count_ptr, float keep_inv) {
+  const float invn = 1.f / (count_ptr ? *count_ptr : (float)count);
+  const long numo = n * (h >> 3);
+  const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const int c = (int)((i0 * 8) % h);
+  float mu[8], is[8], ga[8], p0[8], p1[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    mu[u] = mean[c + u];
+    is[u] = invstd[c + u];
+    ga[u] = gamma[c + u];
+    p0[u] = partials[c + u];
+    p1[u] = partials[h + c + u];
+  }
+  for (long o = i0; o < numo; o += stride) {
+    const long t = o * 8;
+    float gv[8], xv[8];
+    bn_ld8(&g[t], gv);
+    bn_ld8(&x[t], xv);
+    unsigned bits = 0u;
+    if (MODE == 2) {
+      bits = ((const unsigned char*)ym)[o];
+    } else {
+      float yv[8];
+      bn_ld8((const __bf16*)ym + t, yv);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (!(yv[u] <= 0.f)) bits |= 1u << u;
+    }
+    __bf16 ov[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      float gm = gv[u] * keep_inv;
+      if (!((bits >> u) & 1u)) gm = 0.f;
+      const float xhat = (xv[u] - mu[u]) * is[u];
+      ov[u] = (__bf16)(ga[u] * is[u] *
+                       (gm - p0[u] * invn - xhat * p1[u] * invn));
+    }
+    bn_st8(&dx[t], ov);
+  }
+}
+
+static void bn_apply_mask_launch(const __bf16* x, const float* mean,
+                                 const float* invstd, const float* gamma,
+                                 const float* beta, __bf16* y,
+                                 unsigned char* mask, long n, int h,
+                                 float dropout_p,
+                                 const unsigned long long* seed_ptr,
+                                 hipStream_t s) {
+  const int grid = grid_for(n * (h / 8));
+  if (dropout_p > 0.f)
+    bn_apply_mask_kernel<true><<<grid, 256, 0, s>>>(
+        x, mean, invstd, gamma, beta, y, mask, n, h, dropout_p, seed_ptr);
+  else
+    bn_apply_mask_kernel<false><<<grid, 256, 0, s>>>(
+        x, mean, invstd, gamma, beta, y, mask, n, h, 0.f, nullptr);
+}
+
 __global__ void bn_eval_stats_kernel(const float* __restrict__ rm,
                                      const float* __restrict__ rv,
                                      float* __restrict__ mean,
@@ -1357,10 +1820,17 @@ void launch_bn_eval_stats(const float* running_mean, const float* running_var,
 // --- granular launchers for sync-BN (partials are all-reduced across ranks
 // between the stats and apply phases; `count` = GLOBAL row count) ---
 
+// slab: [bn_wide_slab_rows(n, h), 2h] per-call scratch (nullptr when that
+// returns 0) — same convention for every reduction launcher below
 void launch_bn_stats_only(const float* x, long n, int h, float* partials,
-                          hipStream_t s) {
+                          float* slab, hipStream_t s) {
   if (n == 0) {
     HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
+    return;
+  }
+  if (bn_wide_ok(h)) {
+    bn_stats_wide_launch(x, n, h, partials, slab, false, 0.f, 0.f, nullptr,
+                         nullptr, nullptr, nullptr, s);
     return;
   }
   bn_stats_dispatch(x, n, h, partials, s);
@@ -1399,9 +1869,14 @@ void launch_bn_bwd_partials_only(const float* g, const float* x,
                                  const float* y, const float* mean,
                                  const float* invstd, long n, int h, bool relu,
                                  float* partials, float keep_inv,
-                                 hipStream_t s) {
+                                 float* slab, hipStream_t s) {
   if (n == 0) {
     HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
+    return;
+  }
+  if (bn_wide_ok(h)) {
+    bn_bwd_partials_wide_launch(g, x, y, nullptr, mean, invstd, n, h, relu,
+                                partials, slab, nullptr, nullptr, keep_inv, s);
     return;
   }
   bn_bwd_partials_dispatch(g, x, y, mean, invstd, n, h, relu, partials,
@@ -1430,9 +1905,12 @@ void launch_bn_fwd(const float* x, const float* gamma, const float* beta,
                    float* invstd, float* partials, float* y, long n, int h,
                    float momentum, float eps, bool training, bool relu,
                    float dropout_p, const unsigned long long* seed_ptr,
-                   hipStream_t s) {
+                   float* slab, hipStream_t s) {
   if (n == 0) return;
-  if (training) {
+  if (training && bn_wide_ok(h)) {
+    bn_stats_wide_launch(x, n, h, partials, slab, true, eps, momentum, mean,
+                         invstd, running_mean, running_var, s);
+  } else if (training) {
     bn_stats_dispatch(x, n, h, partials, s);
     bn_finalize_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
         partials, n, h, eps, momentum, mean, invstd, running_mean, running_var,
@@ -1457,13 +1935,20 @@ void launch_counter_bump(unsigned long long* c, hipStream_t s) {
 void launch_bn_bwd(const float* g, const float* x, const float* y,
                    const float* mean, const float* invstd, const float* gamma,
                    float* partials, float* dx, float* dgamma, float* dbeta,
-                   long n, int h, bool relu, float keep_inv, hipStream_t s) {
+                   long n, int h, bool relu, float keep_inv, float* slab,
+                   hipStream_t s) {
   if (n == 0) return;
-  bn_bwd_partials_dispatch(g, x, y, mean, invstd, n, h, relu, partials,
-                           keep_inv, s);
+  const bool wide = bn_wide_ok(h);
+  if (wide)
+    bn_bwd_partials_wide_launch(g, x, y, nullptr, mean, invstd, n, h, relu,
+                                partials, slab, dgamma, dbeta, keep_inv, s);
+  else
+    bn_bwd_partials_dispatch(g, x, y, mean, invstd, n, h, relu, partials,
+                             keep_inv, s);
   bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
       g, x, y, mean, invstd, gamma, partials, dx, n, n, h, relu ? 1 : 0,
       nullptr, keep_inv);
+  if (wide) return;  // dgamma/dbeta written with the partials
   bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(partials, dgamma,
                                                          dbeta, h);
 }
@@ -1473,9 +1958,14 @@ void launch_bn_bwd(const float* g, const float* x, const float* y,
 // params and their grads stay fp32 (standard mixed-precision BN). ---
 
 void launch_bn_stats_only16(const void* x, long n, int h, float* partials,
-                            hipStream_t s) {
+                            float* slab, hipStream_t s) {
   if (n == 0) {
     HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
+    return;
+  }
+  if (bn_wide_ok(h)) {
+    bn_stats_wide_launch((const __bf16*)x, n, h, partials, slab, false, 0.f,
+                         0.f, nullptr, nullptr, nullptr, nullptr, s);
     return;
   }
   bn_stats_dispatch((const __bf16*)x, n, h, partials, s);
@@ -1486,15 +1976,23 @@ void launch_bn_fwd16(const void* x, const float* gamma, const float* beta,
                      float* invstd, float* partials, void* y, long n, int h,
                      float momentum, float eps, bool training, bool relu,
                      float dropout_p, const unsigned long long* seed_ptr,
-                     hipStream_t s) {
+                     float* slab, unsigned char* mask, hipStream_t s) {
   if (n == 0) return;
-  if (training) {
+  if (training && bn_wide_ok(h)) {
+    bn_stats_wide_launch((const __bf16*)x, n, h, partials, slab, true, eps,
+                         momentum, mean, invstd, running_mean, running_var, s);
+  } else if (training) {
     bn_stats_dispatch((const __bf16*)x, n, h, partials, s);
     bn_finalize_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
         partials, n, h, eps, momentum, mean, invstd, running_mean, running_var,
         1);
   } else {
     launch_bn_eval_stats(running_mean, running_var, mean, invstd, h, eps, s);
+  }
+  if (mask) {
+    bn_apply_mask_launch((const __bf16*)x, mean, invstd, gamma, beta,
+                         (__bf16*)y, mask, n, h, dropout_p, seed_ptr, s);
+    return;
   }
   if (training && dropout_p > 0.f)
     bn_apply_kernel<__bf16, __bf16, true><<<grid_for(n * h), 256, 0, s>>>(
@@ -1515,7 +2013,7 @@ void launch_bn_finalize_apply16(const void* x, const float* partials,
                                 float eps, bool training, bool relu,
                                 float dropout_p,
                                 const unsigned long long* seed_ptr,
-                                hipStream_t s) {
+                                unsigned char* mask, hipStream_t s) {
   if (training) {
     bn_finalize_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
         partials, n, h, eps, momentum, mean, invstd, running_mean,
@@ -1524,7 +2022,10 @@ void launch_bn_finalize_apply16(const void* x, const float* partials,
     bn_eval_stats_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
         running_mean, running_var, mean, invstd, h, eps);
   }
-  if (n > 0) {
+  if (n > 0 && mask) {
+    bn_apply_mask_launch((const __bf16*)x, mean, invstd, gamma, beta,
+                         (__bf16*)y, mask, n, h, dropout_p, seed_ptr, s);
+  } else if (n > 0) {
     if (training && dropout_p > 0.f)
       bn_apply_kernel<__bf16, __bf16, true><<<grid_for(n * h), 256, 0, s>>>(
           (const __bf16*)x, mean, invstd, gamma, beta, (__bf16*)y, n, h,
@@ -1541,9 +2042,17 @@ void launch_bn_bwd_partials_only16(const void* g, const void* x,
                                    const void* y, const float* mean,
                                    const float* invstd, long n, int h,
                                    bool relu, float* partials, float keep_inv,
+                                   float* slab, const unsigned char* mask,
                                    hipStream_t s) {
   if (n == 0) {
     HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
+    return;
+  }
+  if (bn_wide_ok(h)) {
+    bn_bwd_partials_wide_launch((const __bf16*)g, (const __bf16*)x,
+                                (const __bf16*)y, mask, mean, invstd, n, h,
+                                relu, partials, slab, nullptr, nullptr,
+                                keep_inv, s);
     return;
   }
   bn_bwd_partials_dispatch((const __bf16*)g, (const __bf16*)x,
@@ -1556,8 +2065,19 @@ void launch_bn_bwd_apply_only16(const void* g, const void* x, const void* y,
                                 const float* gamma, const float* partials,
                                 const float* count_ptr, void* dx, long n,
                                 int h, bool relu, float keep_inv,
-                                hipStream_t s) {
+                                const unsigned char* mask, hipStream_t s) {
   if (n == 0) return;
+  if (relu && bn_wide_ok(h)) {
+    if (mask)
+      bn_bwd_apply_wide_kernel<2><<<grid_for(n * (h / 8)), 256, 0, s>>>(
+          (const __bf16*)g, (const __bf16*)x, mask, mean, invstd, gamma,
+          partials, (__bf16*)dx, n, n, h, count_ptr, keep_inv);
+    else
+      bn_bwd_apply_wide_kernel<1><<<grid_for(n * (h / 8)), 256, 0, s>>>(
+          (const __bf16*)g, (const __bf16*)x, y, mean, invstd, gamma,
+          partials, (__bf16*)dx, n, n, h, count_ptr, keep_inv);
+    return;
+  }
   bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
       (const __bf16*)g, (const __bf16*)x, (const __bf16*)y, mean, invstd,
       gamma, partials, (__bf16*)dx, n, n, h, relu ? 1 : 0, count_ptr,
@@ -1568,15 +2088,33 @@ void launch_bn_bwd16(const void* g, const void* x, const void* y,
                      const float* mean, const float* invstd,
                      const float* gamma, float* partials, void* dx,
                      float* dgamma, float* dbeta, long n, int h, bool relu,
-                     float keep_inv, hipStream_t s) {
+                     float keep_inv, float* slab, const unsigned char* mask,
+                     hipStream_t s) {
   if (n == 0) return;
-  bn_bwd_partials_dispatch((const __bf16*)g, (const __bf16*)x,
-                           (const __bf16*)y, mean, invstd, n, h, relu,
-                           partials, keep_inv, s);
-  bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
-      (const __bf16*)g, (const __bf16*)x, (const __bf16*)y, mean, invstd,
-      gamma, partials, (__bf16*)dx, n, n, h, relu ? 1 : 0, nullptr,
-      keep_inv);
+  const bool wide = bn_wide_ok(h);
+  if (wide)
+    bn_bwd_partials_wide_launch((const __bf16*)g, (const __bf16*)x,
+                                (const __bf16*)y, mask, mean, invstd, n, h,
+                                relu, partials, slab, dgamma, dbeta, keep_inv,
+                                s);
+  else
+    bn_bwd_partials_dispatch((const __bf16*)g, (const __bf16*)x,
+                             (const __bf16*)y, mean, invstd, n, h, relu,
+                             partials, keep_inv, s);
+  if (relu && wide && mask)
+    bn_bwd_apply_wide_kernel<2><<<grid_for(n * (h / 8)), 256, 0, s>>>(
+        (const __bf16*)g, (const __bf16*)x, mask, mean, invstd, gamma,
+        partials, (__bf16*)dx, n, n, h, nullptr, keep_inv);
+  else if (relu && wide)
+    bn_bwd_apply_wide_kernel<1><<<grid_for(n * (h / 8)), 256, 0, s>>>(
+        (const __bf16*)g, (const __bf16*)x, y, mean, invstd, gamma, partials,
+        (__bf16*)dx, n, n, h, nullptr, keep_inv);
+  else
+    bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
+        (const __bf16*)g, (const __bf16*)x, (const __bf16*)y, mean, invstd,
+        gamma, partials, (__bf16*)dx, n, n, h, relu ? 1 : 0, nullptr,
+        keep_inv);
+  if (wide) return;  // dgamma/dbeta written with the partials
   bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(partials, dgamma,
                                                          dbeta, h);
 }

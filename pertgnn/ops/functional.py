@@ -492,17 +492,24 @@ class _BNReLUFn(torch.autograd.Function):
             comm.all_reduce_(partials)
             fin = (m.bn_finalize_apply16 if x.dtype == torch.bfloat16
                    else m.bn_finalize_apply)
-            y, save_mean, save_invstd = fin(
+            out = fin(
                 x, partials, gamma, beta, running_mean, running_var,
                 momentum, eps, training, fuse_relu, drop, seed)
         else:
             fwd = (m.bn_relu_fwd16 if x.dtype == torch.bfloat16
                    else m.bn_relu_fwd)
-            y, save_mean, save_invstd = fwd(
+            out = fwd(
                 x, gamma, beta, running_mean, running_var, momentum, eps,
                 training, fuse_relu, drop, seed
             )
-        ctx.save_for_backward(x, gamma, save_mean, save_invstd, y)
+        y, save_mean, save_invstd = out[:3]
+        # the bf16 training forward with ReLU also returns a bit-packed keep
+        # mask [n, h/8] (uint8); the backward reads that instead of y, and
+        # the next layer's linear still holds y for its own wgrad
+        mask = out[3] if len(out) > 3 and out[3].numel() > 0 else None
+        ctx.save_for_backward(x, gamma, save_mean, save_invstd,
+                              y if mask is None else mask)
+        ctx.y16 = y.dtype == torch.bfloat16
         ctx.fuse_relu = fuse_relu
         ctx.comm = comm if sync else None
         # post-dropout y==0 <=> dropped-or-relu-negative, so the backward
@@ -515,7 +522,7 @@ class _BNReLUFn(torch.autograd.Function):
         x, gamma, save_mean, save_invstd, y = ctx.saved_tensors
         m = ext()
         g = g.contiguous()
-        y16 = y.dtype == torch.bfloat16
+        y16 = ctx.y16  # y may be the uint8 keep mask (act16 path only)
         if ctx.comm is not None:
             bwd_partials = m.bn_bwd_partials16 if y16 else m.bn_bwd_partials
             bwd_apply = m.bn_bwd_apply16 if y16 else m.bn_bwd_apply
