@@ -170,6 +170,14 @@ void launch_edge_attn_fused_bwd16(const void*, int, const void*,
                                   int, const float*, const int*, const int*,
                                   const int*, const int*, const int*, void*,
                                   void*, float*, int, int, long, hipStream_t);
+void launch_edge_attn_fused_infer(const float*, const float*, const float*,
+                                  const long*, int, const int*, const int*,
+                                  const float*, const float*, int, float*,
+                                  int, int, hipStream_t);
+void launch_edge_attn_fused_infer16(const void*, const void*, const void*,
+                                    int, const long*, int, const int*,
+                                    const int*, const float*, const float*,
+                                    int, void*, int, int, int, hipStream_t);
 void launch_vocab_scatter_dual16(const void*, const long*, int, float*,
                                  float*, long, int, int, int, hipStream_t);
 void launch_gemm_bf16_nt_o16(const float*, const float*, const float*, void*,
@@ -722,6 +730,76 @@ std::vector<torch::Tensor> edge_attn_fused_fwd(
         n, h, cur_stream());
   }
   return {out, alpha};
+}
+
+// Forward-only fused attention for inference: no alpha, and the eval-mode
+// BatchNorm folded to a per-channel affine (bn_scale/bn_shift, fp32 [h];
+// both empty = no affine) plus the optional ReLU applied in the kernel's
+// epilogue before the single store.
+torch::Tensor edge_attn_fused_infer(
+    torch::Tensor qkvs, torch::Tensor pifc, torch::Tensor prpc,
+    torch::Tensor ea, torch::Tensor row_ptr, torch::Tensor csr_src,
+    torch::Tensor bn_scale, torch::Tensor bn_shift, bool relu, bool out16) {
+  CHECK_IN(qkvs); CHECK_IN(pifc); CHECK_IN(prpc); CHECK_IN(ea);
+  CHECK_IN(row_ptr); CHECK_IN(csr_src);
+  TORCH_CHECK(qkvs.dim() == 2 && qkvs.size(1) % 4 == 0,
+              "qkvs must be [N, 4h]");
+  const int n = qkvs.size(0);
+  const int h = qkvs.size(1) / 4;
+  TORCH_CHECK(qkvs.size(1) == 4 * (int64_t)h, "qkvs must be [N, 4h]");
+  TORCH_CHECK(h <= 512, "H must be <= 512");
+  const bool b16 = qkvs.scalar_type() == torch::kBFloat16;
+  const bool p16 = pifc.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(b16 || qkvs.scalar_type() == torch::kFloat32,
+              "qkvs must be fp32 or bf16");
+  TORCH_CHECK(!out16 || b16, "out16 requires bf16 qkvs");
+  TORCH_CHECK(!p16 || b16, "bf16 P tables require bf16 qkvs");
+  TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(),
+              "P tables must share a dtype");
+  TORCH_CHECK(p16 || pifc.scalar_type() == torch::kFloat32,
+              "P tables must be fp32 or bf16");
+  TORCH_CHECK(pifc.dim() == 2 && prpc.dim() == 2 && pifc.size(1) == h &&
+                  prpc.size(1) == h,
+              "P tables must have width h");
+  TORCH_CHECK(ea.dim() == 2 && ea.size(1) >= 2 &&
+                  ea.scalar_type() == torch::kLong,
+              "edge_attr must be int64 [E, >=2]");
+  TORCH_CHECK(row_ptr.numel() == (int64_t)n + 1 &&
+                  csr_src.numel() == ea.size(0),
+              "CSR arrays do not match qkvs/edge_attr");
+  TORCH_CHECK(bn_scale.numel() == bn_shift.numel() &&
+                  (bn_scale.numel() == 0 || bn_scale.numel() == h),
+              "bn_scale/bn_shift must both be empty or both have h elements");
+  const float* sc = nullptr;
+  const float* sh = nullptr;
+  if (bn_scale.numel() > 0) {
+    TORCH_CHECK(bn_scale.scalar_type() == torch::kFloat32 &&
+                    bn_shift.scalar_type() == torch::kFloat32,
+                "bn_scale/bn_shift must be fp32");
+    TORCH_CHECK(bn_scale.is_contiguous() && bn_shift.is_contiguous(),
+                "bn_scale/bn_shift must be contiguous");
+    TORCH_CHECK(bn_scale.device() == qkvs.device() &&
+                    bn_shift.device() == qkvs.device(),
+                "bn_scale/bn_shift must be on the device of qkvs");
+    sc = bn_scale.data_ptr<float>();
+    sh = bn_shift.data_ptr<float>();
+  }
+  auto fopt = qkvs.options().dtype(torch::kFloat32);
+  auto out = torch::empty({n, h}, out16 ? qkvs.options() : fopt);
+  if (b16) {
+    launch_edge_attn_fused_infer16(
+        qkvs.data_ptr(), pifc.data_ptr(), prpc.data_ptr(), p16 ? 1 : 0,
+        ea.data_ptr<long>(), (int)ea.size(1), row_ptr.data_ptr<int>(),
+        csr_src.data_ptr<int>(), sc, sh, relu ? 1 : 0, out.data_ptr(),
+        out16 ? 1 : 0, n, h, cur_stream());
+  } else {
+    launch_edge_attn_fused_infer(
+        qkvs.data_ptr<float>(), pifc.data_ptr<float>(), prpc.data_ptr<float>(),
+        ea.data_ptr<long>(), (int)ea.size(1), row_ptr.data_ptr<int>(),
+        csr_src.data_ptr<int>(), sc, sh, relu ? 1 : 0, out.data_ptr<float>(),
+        n, h, cur_stream());
+  }
+  return out;
 }
 
 std::vector<torch::Tensor> edge_attn_fused_bwd(
@@ -1305,6 +1383,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::call_guard<py::gil_scoped_release>());
   mod.def("edge_attn_fused_fwd", &edge_attn_fused_fwd);
   mod.def("edge_attn_fused_bwd", &edge_attn_fused_bwd);
+  mod.def("edge_attn_fused_infer", &edge_attn_fused_infer, py::arg("qkvs"),
+          py::arg("pifc"), py::arg("prpc"), py::arg("edge_attr"),
+          py::arg("row_ptr"), py::arg("csr_src"), py::arg("bn_scale"),
+          py::arg("bn_shift"), py::arg("relu"), py::arg("out16"));
   mod.def("embed_grouped_scatter", &embed_grouped_scatter);
   mod.def("linear_fwd", &linear_fwd);
   mod.def("linear_fwd_bf16", &linear_fwd_bf16);

@@ -214,6 +214,86 @@ __global__ void edge_attn_fused_fwd_kernel(
     alpha[p] = __expf(alpha[p] - m) * inv_s;
 }
 
+// Forward-only variant for inference: same row/column mapping and online
+// softmax as the training forward, but nothing is kept for a backward — no
+// alpha tensor, no per-edge logit store, no second pass over the row's
+// edges — and the eval-mode BatchNorm (a fixed per-channel affine, folded
+// on the host into bn_scale/bn_shift) plus the ReLU ride in the epilogue
+// while the row is still in fp32 registers: one store, rounded once.
+// bn_scale == nullptr skips the affine.  Rows without in-edges (s == 0)
+// produce epilogue(skip).
+template <int VPT, bool VEC, typename QT = float, int LPR = PERTGNN_WAVE,
+          typename TO = float, typename PT = float>
+__global__ void edge_attn_fused_infer_kernel(
+    const QT* __restrict__ qkvs,  // [N, 4h]
+    const PT* __restrict__ pifc,  // [Vi, h]
+    const PT* __restrict__ prpc,  // [Vr, h]
+    const long* __restrict__ ea, int astride,
+    const int* __restrict__ row_ptr, const int* __restrict__ csr_src,
+    const float* __restrict__ bn_scale,  // [h] or null
+    const float* __restrict__ bn_shift,  // [h] or null
+    int relu, TO* __restrict__ out, int n, int h, float scale) {
+  using S = Slice<VPT, VEC>;
+  static_assert(VEC || LPR == PERTGNN_WAVE, "sub-wave rows need VEC layout");
+  constexpr int RPW = PERTGNN_WAVE / LPR;
+  const int wid = threadIdx.x / PERTGNN_WAVE;
+  const int lane0 = threadIdx.x % PERTGNN_WAVE;
+  const int sub = lane0 / LPR;
+  const int lane = lane0 % LPR;
+  const int row = (blockIdx.x * WAVES_PER_BLOCK + wid) * RPW + sub;
+  if (row >= n) return;
+  const long ld = 4L * h;
+
+  float qr[VPT], acc[VPT];
+  S::load(&qkvs[row * ld], lane, h, qr);
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) acc[j] = 0.f;
+
+  const int beg = row_ptr[row], end = row_ptr[row + 1];
+  float m = -INFINITY, s = 0.f;
+  for (int p = beg; p < end; ++p) {
+    const long src = csr_src[p];
+    const long a0 = ea[(long)p * astride];
+    const long a1 = ea[(long)p * astride + 1];
+    float ec[VPT], ke[VPT], ve[VPT];
+    // all three gathers issue together, as in the training forward
+    S::load_add(&pifc[a0 * h], &prpc[a1 * h], lane, h, ec);
+    S::load(&qkvs[src * ld + h], lane, h, ke);
+    S::load(&qkvs[src * ld + 2 * h], lane, h, ve);
+    float part = 0.f;
+#pragma unroll
+    for (int j = 0; j < VPT; ++j) part += qr[j] * (ke[j] + ec[j]);
+    const float logit = subwave_reduce_sum<LPR>(part) * scale;
+    const float m_new = fmaxf(m, logit);
+    const float corr = __expf(m - m_new);
+    const float pexp = __expf(logit - m_new);
+    s = s * corr + pexp;
+#pragma unroll
+    for (int j = 0; j < VPT; ++j)
+      acc[j] = acc[j] * corr + pexp * (ve[j] + ec[j]);
+    m = m_new;
+  }
+
+  const float inv_s = (s > 0.f) ? 1.f / s : 0.f;
+  float sk[VPT], res[VPT];
+  S::load(&qkvs[row * ld + 3 * h], lane, h, sk);
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) res[j] = acc[j] * inv_s + sk[j];
+  if (bn_scale != nullptr) {
+    // same Slice mapping as the row: the non-VEC c < h guard covers these
+    float bs[VPT], bb[VPT];
+    S::load(bn_scale, lane, h, bs);
+    S::load(bn_shift, lane, h, bb);
+#pragma unroll
+    for (int j = 0; j < VPT; ++j) res[j] = res[j] * bs[j] + bb[j];
+  }
+  if (relu) {
+#pragma unroll
+    for (int j = 0; j < VPT; ++j) res[j] = fmaxf(res[j], 0.f);
+  }
+  S::store(&out[(long)row * h], lane, h, res);
+}
+
 template <int VPT, bool VEC, typename QT = float,
           int LPR = PERTGNN_WAVE, typename TG = float, typename PT = float>
 __global__ void edge_attn_fused_bwd_row_kernel(
@@ -557,4 +637,102 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
     pertgnn_shape_fail("edge_attn_fused act16 launcher", "h", h);
   }
 #undef BWD16
+}
+
+
+// ---------------------------------------------------------------------------
+// inference launchers (forward-only kernel, folded BN+ReLU epilogue); same
+// shape coverage and kernel selection as the two training forward launchers
+// ---------------------------------------------------------------------------
+
+void launch_edge_attn_fused_infer(const float* qkvs, const float* pifc,
+                                  const float* prpc, const long* ea,
+                                  int astride, const int* row_ptr,
+                                  const int* csr_src, const float* bn_scale,
+                                  const float* bn_shift, int relu, float* out,
+                                  int n, int h, hipStream_t stream) {
+  if (n == 0) return;
+  const float scale = 1.f / std::sqrt((float)h);
+  const dim3 grid(ceil_div(n, WAVES_PER_BLOCK));
+  const dim3 block(WAVES_PER_BLOCK * PERTGNN_WAVE);
+  const int vpt = (h + PERTGNN_WAVE - 1) / PERTGNN_WAVE;
+  const bool vec = (h % 256 == 0);
+  switch (vpt) {
+#define CASE(V)                                                                \
+  case V:                                                                      \
+    if (vec && (V % 4 == 0))                                                   \
+      edge_attn_fused_infer_kernel<V, true><<<grid, block, 0, stream>>>(       \
+          qkvs, pifc, prpc, ea, astride, row_ptr, csr_src, bn_scale,           \
+          bn_shift, relu, out, n, h, scale);                                   \
+    else                                                                       \
+      edge_attn_fused_infer_kernel<V, false><<<grid, block, 0, stream>>>(      \
+          qkvs, pifc, prpc, ea, astride, row_ptr, csr_src, bn_scale,           \
+          bn_shift, relu, out, n, h, scale);                                   \
+    break;
+    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
+#undef CASE
+    default: pertgnn_shape_fail("edge_attn_fused infer launcher", "vpt", vpt);
+  }
+}
+
+void launch_edge_attn_fused_infer16(const void* qkvs_v, const void* pifc_v,
+                                    const void* prpc_v, int p16,
+                                    const long* ea, int astride,
+                                    const int* row_ptr, const int* csr_src,
+                                    const float* bn_scale,
+                                    const float* bn_shift, int relu,
+                                    void* out_v, int out16, int n, int h,
+                                    hipStream_t stream) {
+  const __bf16* qkvs = (const __bf16*)qkvs_v;
+  if (n == 0) return;
+  const float scale = 1.f / std::sqrt((float)h);
+  const dim3 block(WAVES_PER_BLOCK * PERTGNN_WAVE);
+  const int lpr = attn_lpr();
+  const int rpb = WAVES_PER_BLOCK * (PERTGNN_WAVE / lpr);
+  const dim3 grid(ceil_div(n, rpb));
+#define INF16(VPT, LPR)                                                        \
+  do {                                                                         \
+    if (p16 && out16) {                                                        \
+      edge_attn_fused_infer_kernel<VPT, true, __bf16, LPR, __bf16, __bf16>     \
+          <<<grid, block, 0, stream>>>(qkvs, (const __bf16*)pifc_v,            \
+                                       (const __bf16*)prpc_v, ea, astride,     \
+                                       row_ptr, csr_src, bn_scale, bn_shift,   \
+                                       relu, (__bf16*)out_v, n, h, scale);     \
+    } else if (p16) {                                                          \
+      edge_attn_fused_infer_kernel<VPT, true, __bf16, LPR, float, __bf16>      \
+          <<<grid, block, 0, stream>>>(qkvs, (const __bf16*)pifc_v,            \
+                                       (const __bf16*)prpc_v, ea, astride,     \
+                                       row_ptr, csr_src, bn_scale, bn_shift,   \
+                                       relu, (float*)out_v, n, h, scale);      \
+    } else if (out16) {                                                        \
+      edge_attn_fused_infer_kernel<VPT, true, __bf16, LPR, __bf16>             \
+          <<<grid, block, 0, stream>>>(qkvs, (const float*)pifc_v,             \
+                                       (const float*)prpc_v, ea, astride,      \
+                                       row_ptr, csr_src, bn_scale, bn_shift,   \
+                                       relu, (__bf16*)out_v, n, h, scale);     \
+    } else {                                                                   \
+      edge_attn_fused_infer_kernel<VPT, true, __bf16, LPR, float>              \
+          <<<grid, block, 0, stream>>>(qkvs, (const float*)pifc_v,             \
+                                       (const float*)prpc_v, ea, astride,      \
+                                       row_ptr, csr_src, bn_scale, bn_shift,   \
+                                       relu, (float*)out_v, n, h, scale);      \
+    }                                                                          \
+  } while (0)
+  if (h == 256) {
+    if (lpr == 16) INF16(16, 16);
+    else if (lpr == 32) INF16(8, 32);
+    else INF16(4, 64);
+  } else if (h == 512) {
+    if (lpr == 16 || lpr == 32) INF16(16, 32);
+    else INF16(8, 64);
+  } else if (h % 256 == 0 && h / PERTGNN_WAVE <= 32) {
+    const int vpt = h / PERTGNN_WAVE;
+    if (vpt == 4) INF16(4, 64);
+    else if (vpt == 8) INF16(8, 64);
+    else if (vpt == 16) INF16(16, 64);
+    else INF16(32, 64);
+  } else {
+    pertgnn_shape_fail("edge_attn_fused infer act16 launcher", "h", h);
+  }
+#undef INF16
 }

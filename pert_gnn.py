@@ -64,7 +64,60 @@ def build_parser():
                              "composition batches (one seeded shuffle; only the "
                              "batch ORDER reshuffles per epoch — documented "
                              "deviation from the reference's per-epoch re-draw)")
+    parser.add_argument("--predict", type=str, default=None, metavar="OUT.npy",
+                        help="inference mode: load the model from --checkpoint, "
+                             "predict the latency of every trace of "
+                             "--predict_split, write the float32 predictions "
+                             "(split order) with numpy.save, print the split's "
+                             "metrics and exit without training; --hipgraph "
+                             "replays captured forwards")
+    parser.add_argument("--predict_split", default="test",
+                        choices=["test", "valid", "train", "all"],
+                        help="which split --predict runs over ('all' = train, "
+                             "valid, test concatenated)")
+    parser.add_argument("--fast_eval", action="store_true",
+                        help="per-epoch valid/test passes through the inference "
+                             "path (pertgnn.infer.Predictor, refreshed after "
+                             "every training epoch; captured once over the "
+                             "resident eval batches under --hipgraph)")
     return parser
+
+
+def run_predict(args, model, device, samples):
+    """--predict: one pass of ``samples`` through a Predictor over
+    HBM-resident batches; writes the predictions and prints the metrics."""
+    import numpy as np
+
+    from pertgnn.data.collate import collate_native
+    from pertgnn.infer import Predictor
+    from pertgnn.ops import functional as ops
+    from pertgnn.train.capture import make_resident_batches
+
+    resident = make_resident_batches(samples, args.batch_size, device, 0,
+                                     collate_fn=collate_native, shuffle=False)
+    predictor = Predictor(model)
+    if args.hipgraph:
+        mode = predictor.capture(resident)
+        print(f"# predict stepping mode: {mode} "
+              f"({len(resident)} resident batches)")
+    acc = torch.zeros(3, dtype=torch.float64, device=device)
+    preds = []
+    n = 0
+    with torch.no_grad():
+        for i, b in enumerate(resident):
+            pred = (predictor.replay(i) if args.hipgraph
+                    else predictor.predict_batch(b))
+            sums = ops.eval_metrics(b.y, pred, args.tau)
+            for j, v in enumerate(sums):
+                acc[j] += v.double() if torch.is_tensor(v) else v
+            preds.append(pred)
+            n += b.num_graphs
+    out = (torch.cat(preds).cpu() if preds
+           else torch.empty(0, dtype=torch.float32))  # the one host sync
+    mae, mape, qloss = (acc / max(n, 1)).tolist()
+    with open(args.predict, "wb") as f:
+        np.save(f, out.numpy().astype(np.float32, copy=False))
+    print(f"Predict: n={n}, mae={mae!r}, mape={mape!r}, q loss={qloss!r}")
 
 
 def load_artifacts(args, comm=None):
@@ -106,6 +159,13 @@ def main(argv=None):
     print(args)
     comm = Comm()
     torch.manual_seed(args.seed + comm.rank)
+    if args.predict:
+        if comm.distributed:
+            raise SystemExit("--predict runs in a single process; start it "
+                             "without a distributed launcher")
+        if not args.checkpoint or not os.path.exists(args.checkpoint):
+            raise SystemExit("--predict needs an existing --checkpoint "
+                             f"(got {args.checkpoint!r})")
 
     if torch.cuda.is_available():
         # reference semantics: single process honors --device (pert_gnn.py:36);
@@ -173,6 +233,16 @@ def main(argv=None):
     if torch.cuda.is_available():
         from pertgnn.ops.functional import set_gemm_precision
         set_gemm_precision(args.precision)
+    if args.predict:
+        # model state only: no optimizer, no RNG restore
+        state = torch.load(args.checkpoint, map_location=device,
+                           weights_only=False)
+        model.load_state_dict(state["model"])
+        samples = {"test": test_list, "valid": valid_list, "train": train_list,
+                   "all": train_list + valid_list + test_list}[args.predict_split]
+        run_predict(args, model, device, samples)
+        comm.finalize()
+        return
     dynamic_scale = str(args.loss_scale).lower() == "dynamic"
     static_scale = 1.0 if dynamic_scale else float(args.loss_scale)
     args.loss_scale = static_scale  # loops use optimizer.scale_loss anyway
@@ -210,6 +280,17 @@ def main(argv=None):
             test_shard, args.batch_size, device, 0, collate_fn=collate_native,
             shuffle=False)
 
+    predictor = None
+    if args.fast_eval:
+        from pertgnn.infer import Predictor
+
+        was_training = model.training
+        predictor = Predictor(model)
+        model.train(was_training)
+        if args.hipgraph:
+            mode = predictor.capture(list(valid_loader) + list(test_loader))
+            log.print0(f"# fast_eval stepping mode: {mode}")
+
     import time as _time
 
     def run_train_epoch(epoch_stats):
@@ -236,8 +317,12 @@ def main(argv=None):
     for epoch in range(start_epoch, args.epochs + 1):
         epoch_stats: dict = {}
         train_mae, train_mape = run_train_epoch(epoch_stats)
-        valid_mae, valid_mape, valid_q = evaluate(model, valid_loader, args.tau, device, comm=comm)
-        test_mae, test_mape, test_q = evaluate(model, test_loader, args.tau, device, comm=comm)
+        if predictor is not None:
+            predictor.refresh()  # the epoch above changed the weights
+        valid_mae, valid_mape, valid_q = evaluate(
+            model, valid_loader, args.tau, device, comm=comm, predictor=predictor)
+        test_mae, test_mape, test_q = evaluate(
+            model, test_loader, args.tau, device, comm=comm, predictor=predictor)
         # reference epoch line format (pert_gnn.py:348-350)
         log.print0(
             f"Epoch: {epoch}, Train: {train_mae}, Test mae: {test_mae}, "

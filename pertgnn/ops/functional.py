@@ -328,6 +328,36 @@ def edge_attention_fused(qkvs, pifc, prpc, edge_attr, csr, out16=False):
     )
 
 
+def edge_attention_fused_infer(qkvs, pifc, prpc, edge_attr, csr,
+                               bn_scale=None, bn_shift=None, relu=False,
+                               out16=False):
+    """Forward-only ``edge_attention_fused`` for inference (K-inference):
+    saves nothing for a backward, and applies the eval-mode BatchNorm — folded
+    to the per-channel affine ``bn_scale``/``bn_shift`` (fp32 [H], see
+    ``pertgnn.infer.fold_bn``) — and the optional ReLU in the kernel's
+    epilogue, so a non-final layer is one kernel instead of attention plus
+    a BN-apply pass.  NOT differentiable: raises when grad mode is on and an
+    input requires grad.  CPU tensors and PERTGNN_FORCE_EAGER=1 take the
+    fp32 oracle in ``reference``."""
+    if (bn_scale is None) != (bn_shift is None):
+        raise ValueError("bn_scale and bn_shift must be given together")
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad
+            for t in (qkvs, pifc, prpc, bn_scale, bn_shift)):
+        raise RuntimeError(
+            "edge_attention_fused_infer is forward-only (no backward); call "
+            "it under torch.no_grad() or use edge_attention_fused")
+    if not use_hip(qkvs):
+        return ref.edge_attention_fused_infer(
+            qkvs, pifc, prpc, edge_attr, csr, bn_scale, bn_shift, relu, out16)
+    if bn_scale is None:
+        bn_scale = bn_shift = torch.empty(0, dtype=torch.float32,
+                                          device=qkvs.device)
+    return ext().edge_attn_fused_infer(qkvs, pifc, prpc, edge_attr, csr[0],
+                                       csr[1], bn_scale, bn_shift, bool(relu),
+                                       bool(out16))
+
+
 # ---------------------------------------------------------------------------
 # pattern pool (K9+K10)
 # ---------------------------------------------------------------------------
@@ -774,6 +804,7 @@ __all__ = [
     "act16_enabled",
     "edge_attention",
     "edge_attention_fused",
+    "edge_attention_fused_infer",
     "embedding",
     "pattern_pool",
     "embed_concat_node",

@@ -79,6 +79,40 @@ def edge_attention(
     return out
 
 
+def edge_attention_fused_infer(
+    qkvs: torch.Tensor,       # [N,4H]  q | k | v | skip segments
+    pifc: torch.Tensor,       # [Vi,H]  interface_table @ we_ifc^T
+    prpc: torch.Tensor,       # [Vr,H]  rpctype_table  @ we_rpc^T
+    edge_attr: torch.Tensor,  # [E,>=2] int64, CSR (destination-sorted) order
+    csr,                      # (row_ptr, csr_src, ...) from the collator
+    bn_scale: torch.Tensor | None = None,  # [H] folded eval-mode BN scale
+    bn_shift: torch.Tensor | None = None,  # [H] folded eval-mode BN shift
+    relu: bool = False,
+    out16: bool = False,
+):
+    """fp32 oracle of the forward-only fused attention (K-inference):
+    ``edge_attention`` on the four segments of ``qkvs`` with the per-edge
+    embedding P_ifc[a0] + P_rpc[a1], then the folded BatchNorm affine, then
+    the ReLU.  All math is fp32 whatever the input dtypes; ``out16`` rounds
+    the result to bf16 once at the end, like the kernel's single store."""
+    row_ptr, csr_src = csr[0], csr[1]
+    n = qkvs.shape[0]
+    h = qkvs.shape[1] // 4
+    q, k, v, skip = (t.float() for t in qkvs.split(h, dim=1))
+    e = (pifc.float().index_select(0, edge_attr[:, 0])
+         + prpc.float().index_select(0, edge_attr[:, 1]))
+    deg = (row_ptr[1:] - row_ptr[:-1]).long()
+    dst = torch.repeat_interleave(
+        torch.arange(n, dtype=torch.long, device=qkvs.device), deg)
+    edge_index = torch.stack([csr_src.long(), dst])
+    out = edge_attention(q, k, v, e, edge_index, n, skip)
+    if bn_scale is not None:
+        out = out * bn_scale.float() + bn_shift.float()
+    if relu:
+        out = torch.relu(out)
+    return out.to(torch.bfloat16) if out16 else out
+
+
 # ---------------------------------------------------------------------------
 # K1 + K11: categorical embedding sum + feature concat
 # ---------------------------------------------------------------------------

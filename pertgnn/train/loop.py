@@ -111,14 +111,27 @@ def train_epoch(model, loader, optimizer, tau, device, engine=None, comm=None,
 
 
 @torch.no_grad()
-def evaluate(model, loader, tau, device, comm=None):
+def evaluate(model, loader, tau, device, comm=None, predictor=None):
+    """``predictor`` (a ``pertgnn.infer.Predictor`` over ``model``, refreshed
+    since the last weight update) supplies the predictions instead of the
+    model forward; batches it was captured over (the same resident batch
+    objects) replay their graphs.  Metric kernel and accumulation are
+    unchanged."""
     model.eval()
     acc = None  # [mae, mape, qloss] sums on device; one sync per eval pass
     n_graphs = 0
     for batch in loader:
-        b = batch.to(device) if device is not None else batch
-        global_pred, _ = _forward(model, b)
-        pred = global_pred.flatten()
+        ri = predictor.resident_index(batch) if predictor is not None else None
+        if ri is not None:
+            b = batch
+            pred = predictor.replay(ri)
+        else:
+            b = batch.to(device) if device is not None else batch
+            if predictor is not None:
+                pred = predictor.predict_batch(b)
+            else:
+                global_pred, _ = _forward(model, b)
+                pred = global_pred.flatten()
         mae_s, mape_s, q_s = F.eval_metrics(b.y, pred, tau)
         if acc is None:
             acc = torch.zeros(3, dtype=torch.float64, device=pred.device)
