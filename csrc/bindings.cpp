@@ -155,29 +155,31 @@ void launch_vocab_scatter_dual(const float*, const long*, int, float*, float*,
                                long, int, int, int, hipStream_t);
 void launch_edge_attn_fused_fwd(const float*, const float*, const float*,
                                 const long*, int, const int*, const int*,
-                                float*, float*, int, int, hipStream_t);
+                                float*, float*, int, int, int, hipStream_t);
 void launch_edge_attn_fused_bwd(const float*, const float*, const float*,
                                 const float*, const long*, int, const float*,
                                 const int*, const int*, const int*,
                                 const int*, const int*, float*, float*,
-                                float*, int, int, long, hipStream_t);
+                                float*, int, int, long, int, hipStream_t);
 void launch_edge_attn_fused_fwd16(const void*, const void*, const void*,
                                   int, const long*, int, const int*,
                                   const int*, void*, int, float*, int, int,
-                                  hipStream_t);
+                                  int, hipStream_t);
 void launch_edge_attn_fused_bwd16(const void*, int, const void*,
                                   const void*, const void*, int, const long*,
                                   int, const float*, const int*, const int*,
                                   const int*, const int*, const int*, void*,
-                                  void*, float*, int, int, long, hipStream_t);
+                                  void*, float*, int, int, long, int,
+                                  hipStream_t);
 void launch_edge_attn_fused_infer(const float*, const float*, const float*,
                                   const long*, int, const int*, const int*,
                                   const float*, const float*, int, float*,
-                                  int, int, hipStream_t);
+                                  int, int, int, hipStream_t);
 void launch_edge_attn_fused_infer16(const void*, const void*, const void*,
                                     int, const long*, int, const int*,
                                     const int*, const float*, const float*,
-                                    int, void*, int, int, int, hipStream_t);
+                                    int, void*, int, int, int, int,
+                                    hipStream_t);
 void launch_vocab_scatter_dual16(const void*, const long*, int, float*,
                                  float*, long, int, int, int, hipStream_t);
 void launch_gemm_bf16_nt_o16(const float*, const float*, const float*, void*,
@@ -701,11 +703,13 @@ torch::Tensor embed_grouped_scatter_bal(torch::Tensor g, torch::Tensor order,
 std::vector<torch::Tensor> edge_attn_fused_fwd(
     torch::Tensor qkvs, torch::Tensor pifc, torch::Tensor prpc,
     torch::Tensor ea, torch::Tensor row_ptr, torch::Tensor csr_src,
-    bool out16) {
+    bool out16, int64_t heads = 1) {
   CHECK_IN(qkvs); CHECK_IN(pifc); CHECK_IN(prpc); CHECK_IN(ea);
   const int n = qkvs.size(0);
   const int h = qkvs.size(1) / 4;
   TORCH_CHECK(h <= 512, "H must be <= 512");
+  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
+              "heads must divide H (H=", h, ", heads=", heads, ")");
   auto fopt = qkvs.options().dtype(torch::kFloat32);
   const bool b16 = qkvs.scalar_type() == torch::kBFloat16;
   const bool p16 = pifc.scalar_type() == torch::kBFloat16;
@@ -714,20 +718,22 @@ std::vector<torch::Tensor> edge_attn_fused_fwd(
   TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(),
               "P tables must share a dtype");
   auto out = torch::empty({n, h}, out16 ? qkvs.options() : fopt);
-  auto alpha = torch::empty({ea.size(0)}, fopt);
+  // per-(edge, head) attention weights: [E] single-head, [E, heads] otherwise
+  auto alpha = heads == 1 ? torch::empty({ea.size(0)}, fopt)
+                          : torch::empty({ea.size(0), heads}, fopt);
   if (b16) {
     launch_edge_attn_fused_fwd16(
         qkvs.data_ptr(), pifc.data_ptr(), prpc.data_ptr(), p16 ? 1 : 0,
         ea.data_ptr<long>(), (int)ea.size(1),
         row_ptr.data_ptr<int>(), csr_src.data_ptr<int>(),
         out.data_ptr(), out16 ? 1 : 0, alpha.data_ptr<float>(), n, h,
-        cur_stream());
+        (int)heads, cur_stream());
   } else {
     launch_edge_attn_fused_fwd(
         qkvs.data_ptr<float>(), pifc.data_ptr<float>(), prpc.data_ptr<float>(),
         ea.data_ptr<long>(), (int)ea.size(1), row_ptr.data_ptr<int>(),
         csr_src.data_ptr<int>(), out.data_ptr<float>(), alpha.data_ptr<float>(),
-        n, h, cur_stream());
+        n, h, (int)heads, cur_stream());
   }
   return {out, alpha};
 }
@@ -739,7 +745,8 @@ std::vector<torch::Tensor> edge_attn_fused_fwd(
 torch::Tensor edge_attn_fused_infer(
     torch::Tensor qkvs, torch::Tensor pifc, torch::Tensor prpc,
     torch::Tensor ea, torch::Tensor row_ptr, torch::Tensor csr_src,
-    torch::Tensor bn_scale, torch::Tensor bn_shift, bool relu, bool out16) {
+    torch::Tensor bn_scale, torch::Tensor bn_shift, bool relu, bool out16,
+    int64_t heads = 1) {
   CHECK_IN(qkvs); CHECK_IN(pifc); CHECK_IN(prpc); CHECK_IN(ea);
   CHECK_IN(row_ptr); CHECK_IN(csr_src);
   TORCH_CHECK(qkvs.dim() == 2 && qkvs.size(1) % 4 == 0,
@@ -748,6 +755,8 @@ torch::Tensor edge_attn_fused_infer(
   const int h = qkvs.size(1) / 4;
   TORCH_CHECK(qkvs.size(1) == 4 * (int64_t)h, "qkvs must be [N, 4h]");
   TORCH_CHECK(h <= 512, "H must be <= 512");
+  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
+              "heads must divide H (H=", h, ", heads=", heads, ")");
   const bool b16 = qkvs.scalar_type() == torch::kBFloat16;
   const bool p16 = pifc.scalar_type() == torch::kBFloat16;
   TORCH_CHECK(b16 || qkvs.scalar_type() == torch::kFloat32,
@@ -791,13 +800,13 @@ torch::Tensor edge_attn_fused_infer(
         qkvs.data_ptr(), pifc.data_ptr(), prpc.data_ptr(), p16 ? 1 : 0,
         ea.data_ptr<long>(), (int)ea.size(1), row_ptr.data_ptr<int>(),
         csr_src.data_ptr<int>(), sc, sh, relu ? 1 : 0, out.data_ptr(),
-        out16 ? 1 : 0, n, h, cur_stream());
+        out16 ? 1 : 0, n, h, (int)heads, cur_stream());
   } else {
     launch_edge_attn_fused_infer(
         qkvs.data_ptr<float>(), pifc.data_ptr<float>(), prpc.data_ptr<float>(),
         ea.data_ptr<long>(), (int)ea.size(1), row_ptr.data_ptr<int>(),
         csr_src.data_ptr<int>(), sc, sh, relu ? 1 : 0, out.data_ptr<float>(),
-        n, h, cur_stream());
+        n, h, (int)heads, cur_stream());
   }
   return out;
 }
@@ -806,11 +815,16 @@ std::vector<torch::Tensor> edge_attn_fused_bwd(
     torch::Tensor g, torch::Tensor qkvs, torch::Tensor pifc,
     torch::Tensor prpc, torch::Tensor ea, torch::Tensor alpha,
     torch::Tensor row_ptr, torch::Tensor csr_src, torch::Tensor col_ptr,
-    torch::Tensor csc_dst, torch::Tensor csc_eid) {
+    torch::Tensor csc_dst, torch::Tensor csc_eid, int64_t heads = 1) {
   CHECK_IN(g); CHECK_IN(qkvs); CHECK_IN(alpha);
   const int n = qkvs.size(0);
   const int h = qkvs.size(1) / 4;
   const long ne = ea.size(0);
+  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
+              "heads must divide H (H=", h, ", heads=", heads, ")");
+  TORCH_CHECK(alpha.scalar_type() == torch::kFloat32 &&
+                  alpha.numel() == ne * heads,
+              "alpha must be the fp32 [E, heads] tensor of the forward");
   auto fopt = qkvs.options().dtype(torch::kFloat32);
   auto dqkvs = torch::empty_like(qkvs);
   const bool b16 = qkvs.scalar_type() == torch::kBFloat16;
@@ -819,7 +833,7 @@ std::vector<torch::Tensor> edge_attn_fused_bwd(
   // col kernel regenerates the rank-1 per-edge grads from the per-edge
   // scalars (dal = logit grad, alpha) and row gathers of q/g
   auto de = torch::empty({ne, h}, eopt);
-  auto dal = torch::empty({ne}, fopt);
+  auto dal = torch::empty({ne * heads}, fopt);  // [E, heads] row-major
   if (b16) {
     const int g16 = g.scalar_type() == torch::kBFloat16 ? 1 : 0;
     const int p16 = pifc.scalar_type() == torch::kBFloat16 ? 1 : 0;
@@ -829,7 +843,8 @@ std::vector<torch::Tensor> edge_attn_fused_bwd(
         (int)ea.size(1), alpha.data_ptr<float>(), row_ptr.data_ptr<int>(),
         csr_src.data_ptr<int>(), col_ptr.data_ptr<int>(),
         csc_dst.data_ptr<int>(), csc_eid.data_ptr<int>(), dqkvs.data_ptr(),
-        de.data_ptr(), dal.data_ptr<float>(), n, h, ne, cur_stream());
+        de.data_ptr(), dal.data_ptr<float>(), n, h, ne, (int)heads,
+        cur_stream());
   } else {
     launch_edge_attn_fused_bwd(
         g.data_ptr<float>(), qkvs.data_ptr<float>(), pifc.data_ptr<float>(),
@@ -838,7 +853,7 @@ std::vector<torch::Tensor> edge_attn_fused_bwd(
         csr_src.data_ptr<int>(), col_ptr.data_ptr<int>(),
         csc_dst.data_ptr<int>(), csc_eid.data_ptr<int>(),
         dqkvs.data_ptr<float>(), de.data_ptr<float>(), dal.data_ptr<float>(),
-        n, h, ne, cur_stream());
+        n, h, ne, (int)heads, cur_stream());
   }
   return {dqkvs, de};
 }
@@ -1381,12 +1396,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("vocab_scatter", &vocab_scatter);
   mod.def("collate_native", &collate_native,
           py::call_guard<py::gil_scoped_release>());
-  mod.def("edge_attn_fused_fwd", &edge_attn_fused_fwd);
-  mod.def("edge_attn_fused_bwd", &edge_attn_fused_bwd);
+  mod.def("edge_attn_fused_fwd", &edge_attn_fused_fwd, py::arg("qkvs"),
+          py::arg("pifc"), py::arg("prpc"), py::arg("edge_attr"),
+          py::arg("row_ptr"), py::arg("csr_src"), py::arg("out16"),
+          py::arg("heads") = 1);
+  mod.def("edge_attn_fused_bwd", &edge_attn_fused_bwd, py::arg("g"),
+          py::arg("qkvs"), py::arg("pifc"), py::arg("prpc"),
+          py::arg("edge_attr"), py::arg("alpha"), py::arg("row_ptr"),
+          py::arg("csr_src"), py::arg("col_ptr"), py::arg("csc_dst"),
+          py::arg("csc_eid"), py::arg("heads") = 1);
   mod.def("edge_attn_fused_infer", &edge_attn_fused_infer, py::arg("qkvs"),
           py::arg("pifc"), py::arg("prpc"), py::arg("edge_attr"),
           py::arg("row_ptr"), py::arg("csr_src"), py::arg("bn_scale"),
-          py::arg("bn_shift"), py::arg("relu"), py::arg("out16"));
+          py::arg("bn_shift"), py::arg("relu"), py::arg("out16"),
+          py::arg("heads") = 1);
   mod.def("embed_grouped_scatter", &embed_grouped_scatter);
   mod.def("linear_fwd", &linear_fwd);
   mod.def("linear_fwd_bf16", &linear_fwd_bf16);

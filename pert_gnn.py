@@ -21,6 +21,7 @@ from pertgnn.models import SAGEDeterministic
 from pertgnn.parallel import Comm
 from pertgnn.train.optim import FlatGradAllReduce, FusedAdam
 from pertgnn.train import evaluate, load_checkpoint, save_checkpoint, train_epoch
+from pertgnn.train.checkpoint import check_heads
 from pertgnn.utils import JsonlLogger
 
 
@@ -75,6 +76,11 @@ def build_parser():
                         choices=["test", "valid", "train", "all"],
                         help="which split --predict runs over ('all' = train, "
                              "valid, test concatenated)")
+    parser.add_argument("--heads", type=int, default=1,
+                        help="attention heads per conv (must divide "
+                             "--hidden_channels; 1 = the reference model). "
+                             "Recorded in the checkpoint: resuming or "
+                             "predicting with another value is refused")
     parser.add_argument("--fast_eval", action="store_true",
                         help="per-epoch valid/test passes through the inference "
                              "path (pertgnn.infer.Predictor, refreshed after "
@@ -226,6 +232,7 @@ def main(argv=None):
     model = SAGEDeterministic(
         num_features + 1, [unique_ms_max + 1], entry_id_max, interface_id_max,
         rpctype_id_max, args.hidden_channels, args.num_layers, args.dropout,
+        heads=args.heads,
     ).to(device)
     comm.broadcast_module_(model)
     if args.sync_bn and comm.distributed:
@@ -237,6 +244,7 @@ def main(argv=None):
         # model state only: no optimizer, no RNG restore
         state = torch.load(args.checkpoint, map_location=device,
                            weights_only=False)
+        check_heads(state, model, args.checkpoint)
         model.load_state_dict(state["model"])
         samples = {"test": test_list, "valid": valid_list, "train": train_list,
                    "all": train_list + valid_list + test_list}[args.predict_split]

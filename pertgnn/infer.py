@@ -152,10 +152,11 @@ class Predictor:
                 scale, shift = self.bn_affine[i]
                 x = ops.edge_attention_fused_infer(
                     qkvs, pifc, prpc, edge_attr, csr, scale, shift,
-                    relu=True, out16=act16)
+                    relu=True, out16=act16, heads=conv.heads)
             else:
                 x = ops.edge_attention_fused_infer(qkvs, pifc, prpc,
-                                                   edge_attr, csr)
+                                                   edge_attr, csr,
+                                                   heads=conv.heads)
         num_graphs = b.num_graphs
         mean_x = ops.pattern_pool(x, b.rt_probs, b.pattern_num_nodes, b.batch,
                                   num_graphs)

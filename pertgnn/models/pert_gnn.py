@@ -65,11 +65,22 @@ class _SegLinearView:
 
 
 class TransformerConv(nn.Module):
-    """Graph transformer conv, PyG-2.4.0 semantics with heads=1, concat=True,
-    root_weight=True, beta=False (reference model.py:25-52 configuration).
+    """Graph transformer conv, PyG-2.4.0 semantics with concat=True,
+    root_weight=True, beta=False (reference model.py:25-52 configuration,
+    which uses heads=1).
 
     out_i = W_skip x_i + b + sum_{e:(j->i)} softmax_i(<W_q x_i, W_k x_j + W_e e_ij>/sqrt(H))
             * (W_v x_j + W_e e_ij)
+
+    ``out_channels`` is the TOTAL output width H (the reference passes
+    heads=1, where PyG's per-head width and the total coincide).  With
+    ``heads`` > 1 the H channels split into ``heads`` heads of
+    C = H / heads channels: head t owns channels [tC, (t+1)C), its logits
+    are scaled by 1/sqrt(C) and its softmax runs on its own.  That is PyG's
+    ``TransformerConv(in, C, heads=heads, concat=True, edge_dim=2H)``:
+    the same parameter shapes and state_dict keys at any head count
+    (``lin_*.weight`` [H, in], ``lin_edge.weight`` [H, 2H]), and glorot
+    init over the same shapes.  ``heads`` must divide ``out_channels``.
 
     The four projection matrices live in ONE fused parameter ``w4`` [4H, Kp]
     (rows: query, key, value, skip; Kp = K padded to a multiple of 8 with
@@ -82,7 +93,10 @@ class TransformerConv(nn.Module):
 
     def __init__(self, in_channels: int, out_channels: int, heads: int = 1, edge_dim: int | None = None):
         super().__init__()
-        assert heads == 1, "reference configuration uses heads=1 (model.py:29)"
+        if not isinstance(heads, int) or heads < 1 or out_channels % heads != 0:
+            raise ValueError(
+                f"heads={heads!r} must be a positive integer that divides "
+                f"out_channels={out_channels}")
         self.in_channels = in_channels
         self.out_channels = out_channels
         self.heads = heads
@@ -193,7 +207,8 @@ class TransformerConv(nn.Module):
         v = ops.linear(x, self.lin_value.weight.contiguous(), self.lin_value.bias)
         e = ops.linear(edge_embeds, self.lin_edge.weight, None)
         skip = ops.linear(x, self.lin_skip.weight.contiguous(), self.lin_skip.bias)
-        return ops.edge_attention(q, k, v, e, skip, edge_index, n, csr=csr)
+        return ops.edge_attention(q, k, v, e, skip, edge_index, n, csr=csr,
+                                  heads=self.heads)
 
     def forward_fused(self, x, edge_attr, ifc_weight, rpc_weight, csr,
                       out16=False):
@@ -227,11 +242,13 @@ class TransformerConv(nn.Module):
             pifc = ops.linear(ifc_weight, self.we_ifc, None)
             prpc = ops.linear(rpc_weight, self.we_rpc, None)
         return ops.edge_attention_fused(qkvs, pifc, prpc, edge_attr, csr,
-                                        out16=out16)
+                                        out16=out16, heads=self.heads)
 
 
 class SAGEDeterministic(nn.Module):
-    """API- and checkpoint-compatible with reference model.py:10-114."""
+    """API- and checkpoint-compatible with reference model.py:10-114.
+    ``heads`` (keyword-only, default 1 = the reference) is the attention
+    head count of every conv; it must divide ``hidden_channels``."""
 
     def __init__(
         self,
@@ -243,14 +260,17 @@ class SAGEDeterministic(nn.Module):
         hidden_channels,
         num_layers,
         dropout,
+        *,
+        heads=1,
     ):
         super().__init__()
+        self.heads = heads
         self.convs = nn.ModuleList()
         self.convs.append(
             TransformerConv(
                 in_channels=in_channels + hidden_channels,
                 out_channels=hidden_channels,
-                heads=1,
+                heads=heads,
                 edge_dim=hidden_channels * 2,
             )
         )
@@ -261,7 +281,7 @@ class SAGEDeterministic(nn.Module):
                 TransformerConv(
                     in_channels=hidden_channels,
                     out_channels=hidden_channels,
-                    heads=1,
+                    heads=heads,
                     edge_dim=hidden_channels * 2,
                 )
             )
@@ -270,7 +290,7 @@ class SAGEDeterministic(nn.Module):
             TransformerConv(
                 in_channels=hidden_channels,
                 out_channels=hidden_channels,
-                heads=1,
+                heads=heads,
                 edge_dim=hidden_channels * 2,
             )
         )

@@ -180,8 +180,17 @@ def _device_csr(edge_index, num_nodes):
     return perm, csr
 
 
-def edge_attention(q, k, v, e, skip, edge_index, num_nodes, csr=None):
+def edge_attention(q, k, v, e, skip, edge_index, num_nodes, csr=None,
+                   heads=1):
     """out_i = skip_i + sum_e softmax_i(<q_i, k_src+e>/sqrt(H)) (v_src+e).
+
+    ``heads`` > 1 (concat, C = H/heads): the same formula per head on its
+    channel slice, scaled by 1/sqrt(C).  The reference-layout HIP kernel
+    behind this op is the op-parity path and stays single-head, so on device
+    tensors it runs ONCE PER HEAD on contiguous channel slices and the
+    results are concatenated — correct, not fast (heads x the launches and
+    index traffic, plus the slice copies).  The production path is
+    ``edge_attention_fused``, whose kernels are multi-head natively.
 
     ``csr``: (row_ptr, csr_src, col_ptr, csc_dst, csc_eid) from the collator
     (edges already CSR-ordered).  When absent on the HIP path — the reference
@@ -194,8 +203,22 @@ def edge_attention(q, k, v, e, skip, edge_index, num_nodes, csr=None):
             perm, csr = _device_csr(edge_index, num_nodes)
             e = e.index_select(0, perm)
         row_ptr, csr_src, col_ptr, csc_dst, csc_eid = csr
-        return _EdgeAttentionFn.apply(q, k, v, e, skip, row_ptr, csr_src, col_ptr, csc_dst, csc_eid)
-    return ref.edge_attention(q, k, v, e, edge_index, num_nodes, skip)
+        if heads == 1:
+            return _EdgeAttentionFn.apply(q, k, v, e, skip, row_ptr, csr_src, col_ptr, csc_dst, csc_eid)
+        h = q.shape[1]
+        if heads < 1 or h % heads != 0:
+            raise ValueError(f"heads={heads} does not divide H={h}")
+        c = h // heads
+        outs = [
+            _EdgeAttentionFn.apply(
+                *(t[:, i * c:(i + 1) * c].contiguous()
+                  for t in (q, k, v, e, skip)),
+                row_ptr, csr_src, col_ptr, csc_dst, csc_eid)
+            for i in range(heads)
+        ]
+        return torch.cat(outs, dim=1)
+    return ref.edge_attention(q, k, v, e, edge_index, num_nodes, skip,
+                              heads=heads)
 
 
 class _Linear16Fn(torch.autograd.Function):
@@ -266,11 +289,12 @@ def act16_enabled() -> bool:
 class _EdgeAttentionFusedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkvs, pifc, prpc, edge_attr, row_ptr, csr_src, col_ptr,
-                csc_dst, csc_eid, out16=False):
+                csc_dst, csc_eid, out16=False, heads=1):
         m = ext()
-        out, alpha = m.edge_attn_fused_fwd(qkvs, pifc, prpc, edge_attr, row_ptr, csr_src, out16)
+        out, alpha = m.edge_attn_fused_fwd(qkvs, pifc, prpc, edge_attr, row_ptr, csr_src, out16, heads)
         ctx.save_for_backward(qkvs, pifc, prpc, edge_attr, alpha,
                               row_ptr, csr_src, col_ptr, csc_dst, csc_eid)
+        ctx.heads = heads
         return out
 
     @staticmethod
@@ -280,7 +304,7 @@ class _EdgeAttentionFusedFn(torch.autograd.Function):
         m = ext()
         dqkvs, de = m.edge_attn_fused_bwd(
             g.contiguous(), qkvs, pifc, prpc, edge_attr, alpha,
-            row_ptr, csr_src, col_ptr, csc_dst, csc_eid,
+            row_ptr, csr_src, col_ptr, csc_dst, csc_eid, ctx.heads,
         )
         # dP tables (per-vocab segment sums of de) are independent of the
         # CSC dk/dv pass queued above — overlap them on the side stream.
@@ -295,7 +319,7 @@ class _EdgeAttentionFusedFn(torch.autograd.Function):
             if dpifc.dtype != pifc.dtype:  # bf16 P tables: match grad dtype
                 dpifc = dpifc.to(pifc.dtype)
                 dprpc = dprpc.to(prpc.dtype)
-            return dqkvs, dpifc, dprpc, None, None, None, None, None, None, None
+            return dqkvs, dpifc, dprpc, None, None, None, None, None, None, None, None
         cur = torch.cuda.current_stream()
         side = _side_stream()
         ev = torch.cuda.Event()
@@ -312,25 +336,48 @@ class _EdgeAttentionFusedFn(torch.autograd.Function):
         cur.wait_event(ev2)
         _mark_cross_stream(dpifc, cur)
         _mark_cross_stream(dprpc, cur)
-        return dqkvs, dpifc, dprpc, None, None, None, None, None, None, None
+        return dqkvs, dpifc, dprpc, None, None, None, None, None, None, None, None
 
 
-def edge_attention_fused(qkvs, pifc, prpc, edge_attr, csr, out16=False):
-    """HIP-only fast path: out_i = skip_i + softmax-weighted aggregate where
+def _fused_eager(qkvs, pifc, prpc, edge_attr, csr, heads):
+    """Differentiable fp32 composition of the fused op from the oracle."""
+    row_ptr, csr_src = csr[0], csr[1]
+    n = qkvs.shape[0]
+    h = qkvs.shape[1] // 4
+    q, k, v, skip = qkvs.float().split(h, dim=1)
+    e = (pifc.float().index_select(0, edge_attr[:, 0])
+         + prpc.float().index_select(0, edge_attr[:, 1]))
+    deg = (row_ptr[1:] - row_ptr[:-1]).long()
+    dst = torch.repeat_interleave(
+        torch.arange(n, dtype=torch.long, device=qkvs.device), deg)
+    edge_index = torch.stack([csr_src.long(), dst])
+    return ref.edge_attention(q, k, v, e, edge_index, n, skip, heads=heads)
+
+
+def edge_attention_fused(qkvs, pifc, prpc, edge_attr, csr, out16=False,
+                         heads=1):
+    """Fast path: out_i = skip_i + softmax-weighted aggregate where
     q/k/v/skip are the four H-segments of ``qkvs`` and the edge embedding is
     P_ifc[a0] + P_rpc[a1] (exact refactoring of lin_edge(concat(ifc, rpc))).
     ``out16`` writes the aggregate bf16 (non-final layers feed BN, whose
-    act16 path consumes/produces bf16 streams)."""
+    act16 path consumes/produces bf16 streams).  ``heads`` > 1 splits H into
+    that many heads of C = H/heads channels (concat), each with its own
+    softmax and a 1/sqrt(C) scale; the kernels raise the shape error for a
+    (H, heads) pair their lane mapping cannot express.  CPU tensors and
+    PERTGNN_FORCE_EAGER=1 take the fp32 oracle in ``reference``."""
+    if not use_hip(qkvs):
+        out = _fused_eager(qkvs, pifc, prpc, edge_attr, csr, heads)
+        return out.to(torch.bfloat16) if out16 else out
     row_ptr, csr_src, col_ptr, csc_dst, csc_eid = csr
     return _EdgeAttentionFusedFn.apply(
         qkvs, pifc, prpc, edge_attr, row_ptr, csr_src, col_ptr, csc_dst,
-        csc_eid, out16
+        csc_eid, out16, heads
     )
 
 
 def edge_attention_fused_infer(qkvs, pifc, prpc, edge_attr, csr,
                                bn_scale=None, bn_shift=None, relu=False,
-                               out16=False):
+                               out16=False, heads=1):
     """Forward-only ``edge_attention_fused`` for inference (K-inference):
     saves nothing for a backward, and applies the eval-mode BatchNorm — folded
     to the per-channel affine ``bn_scale``/``bn_shift`` (fp32 [H], see
@@ -338,7 +385,7 @@ def edge_attention_fused_infer(qkvs, pifc, prpc, edge_attr, csr,
     epilogue, so a non-final layer is one kernel instead of attention plus
     a BN-apply pass.  NOT differentiable: raises when grad mode is on and an
     input requires grad.  CPU tensors and PERTGNN_FORCE_EAGER=1 take the
-    fp32 oracle in ``reference``."""
+    fp32 oracle in ``reference``.  ``heads`` as in ``edge_attention_fused``."""
     if (bn_scale is None) != (bn_shift is None):
         raise ValueError("bn_scale and bn_shift must be given together")
     if torch.is_grad_enabled() and any(
@@ -349,13 +396,14 @@ def edge_attention_fused_infer(qkvs, pifc, prpc, edge_attr, csr,
             "it under torch.no_grad() or use edge_attention_fused")
     if not use_hip(qkvs):
         return ref.edge_attention_fused_infer(
-            qkvs, pifc, prpc, edge_attr, csr, bn_scale, bn_shift, relu, out16)
+            qkvs, pifc, prpc, edge_attr, csr, bn_scale, bn_shift, relu, out16,
+            heads)
     if bn_scale is None:
         bn_scale = bn_shift = torch.empty(0, dtype=torch.float32,
                                           device=qkvs.device)
     return ext().edge_attn_fused_infer(qkvs, pifc, prpc, edge_attr, csr[0],
                                        csr[1], bn_scale, bn_shift, bool(relu),
-                                       bool(out16))
+                                       bool(out16), int(heads))
 
 
 # ---------------------------------------------------------------------------

@@ -4,8 +4,8 @@ These are the numerical oracle: each HIP kernel is tested against the function
 here of the same name (fp32, deterministic).  The math mirrors the reference
 repo's dependency-internal op surface (kernels K1–K14):
 
-  * edge attention  = PyG 2.4.0 TransformerConv semantics with heads=1
-    (reference model.py:25-52):
+  * edge attention  = PyG 2.4.0 TransformerConv semantics (reference
+    model.py:25-52 uses heads=1; per-head form in ``edge_attention``):
       out_i = W_skip x_i + b_skip
             + sum_e softmax_i(<q_i, k_src(e)+e_e>/sqrt(H)) * (v_src(e)+e_e)
   * segment softmax = torch_geometric.utils.softmax (max-subtracted, per dst)
@@ -48,7 +48,7 @@ def scatter_sum(src: torch.Tensor, index: torch.Tensor, dim_size: int) -> torch.
 
 
 # ---------------------------------------------------------------------------
-# K3-K6: fused edge attention (TransformerConv heads=1 semantics)
+# K3-K6: fused edge attention (TransformerConv semantics, concat heads)
 # ---------------------------------------------------------------------------
 
 def edge_attention(
@@ -60,13 +60,40 @@ def edge_attention(
     num_nodes: int,
     skip: torch.Tensor | None = None,  # [N,H] W_skip x + b — added to output
     return_alpha: bool = False,
+    heads: int = 1,
 ):
-    """PyG-2.4.0 TransformerConv message+aggregate with heads=1.
+    """PyG-2.4.0 TransformerConv message+aggregate (concat=True).
 
-    Reference call site: model.py:100,104 via SURVEY.md §2.3 semantics.
+    Reference call site: model.py:100,104 via SURVEY.md §2.3 semantics
+    (the reference model uses heads=1).  With ``heads`` > 1 head ``t`` owns
+    channels ``[tC, (t+1)C)``, ``C = H / heads``:
+
+        logit[e,t] = <q_dst[t], (k_src + e_e)[t]> / sqrt(C)
+        alpha[:,t] = softmax over the in-edges of dst, per head
+        out_dst[t] = skip_dst[t] + sum_e alpha[e,t] * (v_src + e_e)[t]
+
+    ``return_alpha`` gives alpha as [E] for heads=1 and [E,heads] otherwise.
     """
     src, dst = edge_index[0], edge_index[1]
     h = q.shape[1]
+    if heads != 1:
+        if heads < 1 or h % heads != 0:
+            raise ValueError(f"heads={heads} does not divide H={h}")
+        c = h // heads
+        ke = (k.index_select(0, src) + e).view(-1, heads, c)
+        ve = (v.index_select(0, src) + e).view(-1, heads, c)
+        qd = q.index_select(0, dst).view(-1, heads, c)
+        logits = (qd * ke).sum(-1) / math.sqrt(c)          # [E,heads]
+        alpha = torch.stack(
+            [segment_softmax(logits[:, t], dst, num_nodes)
+             for t in range(heads)], dim=1)
+        out = scatter_sum((alpha.unsqueeze(-1) * ve).reshape(-1, h), dst,
+                          num_nodes)
+        if skip is not None:
+            out = out + skip
+        if return_alpha:
+            return out, alpha
+        return out
     ke = k.index_select(0, src) + e
     ve = v.index_select(0, src) + e
     logits = (q.index_select(0, dst) * ke).sum(-1) / math.sqrt(h)
@@ -89,6 +116,7 @@ def edge_attention_fused_infer(
     bn_shift: torch.Tensor | None = None,  # [H] folded eval-mode BN shift
     relu: bool = False,
     out16: bool = False,
+    heads: int = 1,
 ):
     """fp32 oracle of the forward-only fused attention (K-inference):
     ``edge_attention`` on the four segments of ``qkvs`` with the per-edge
@@ -105,7 +133,7 @@ def edge_attention_fused_infer(
     dst = torch.repeat_interleave(
         torch.arange(n, dtype=torch.long, device=qkvs.device), deg)
     edge_index = torch.stack([csr_src.long(), dst])
-    out = edge_attention(q, k, v, e, edge_index, n, skip)
+    out = edge_attention(q, k, v, e, edge_index, n, skip, heads=heads)
     if bn_scale is not None:
         out = out * bn_scale.float() + bn_shift.float()
     if relu:

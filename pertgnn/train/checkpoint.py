@@ -2,14 +2,38 @@
 
 Checkpoint = model state_dict (keyed identically to the reference
 SAGEDeterministic, including the dead ``edge_linear`` lazy module, quirk 4)
-+ optimizer state + RNG states + epoch counter.  Rank 0 writes; all ranks
-barrier; every rank loads.
++ optimizer state + RNG states + epoch counter + the attention head count.
+Rank 0 writes; all ranks barrier; every rank loads.
+
+A state_dict has the same keys and shapes at every head count, so loading a
+heads=4 checkpoint into a heads=1 model would succeed and silently compute
+something else.  The checkpoint therefore records ``heads`` and
+``load_checkpoint`` refuses a mismatch; a checkpoint without the field was
+written before the field existed and means ``heads=1``.
 """
 from __future__ import annotations
 
 import os
 
 import torch
+
+
+def model_heads(model) -> int:
+    """Attention head count of a model (1 when it has no such notion)."""
+    return int(getattr(model, "heads", 1))
+
+
+def check_heads(state: dict, model, path: str = "checkpoint"):
+    """Raise when the head count recorded in ``state`` differs from the
+    model's (missing field = 1)."""
+    saved = int(state.get("heads", 1))
+    have = model_heads(model)
+    if saved != have:
+        raise ValueError(
+            f"{path} was written by a model with heads={saved}, but the "
+            f"model to load it into has heads={have}; the weights have the "
+            "same shapes at any head count and would load silently — build "
+            f"the model with heads={saved}")
 
 
 def save_checkpoint(path: str, model, optimizer, epoch: int, comm=None, extra: dict | None = None):
@@ -19,6 +43,7 @@ def save_checkpoint(path: str, model, optimizer, epoch: int, comm=None, extra: d
             "model": model.state_dict(),
             "optimizer": optimizer.state_dict() if optimizer is not None else None,
             "epoch": epoch,
+            "heads": model_heads(model),
             "rng": {
                 "torch": torch.get_rng_state(),
                 "cuda": torch.cuda.get_rng_state_all() if torch.cuda.is_available() else None,
@@ -34,6 +59,7 @@ def save_checkpoint(path: str, model, optimizer, epoch: int, comm=None, extra: d
 
 def load_checkpoint(path: str, model, optimizer=None, map_location="cpu"):
     state = torch.load(path, map_location=map_location, weights_only=False)
+    check_heads(state, model, path)
     model.load_state_dict(state["model"])
     if optimizer is not None and state.get("optimizer") is not None:
         optimizer.load_state_dict(state["optimizer"])
