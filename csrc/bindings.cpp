@@ -149,6 +149,8 @@ void launch_embed_grouped_scatter_bal(const void*, int, const int*,
                                       const int*, const int*, float*, float*,
                                       float*, int, int, int, int, int, int,
                                       hipStream_t);
+void launch_rows_sum_lists(const void*, int, const int*, const int*, void*, int,
+                           int, int, int, hipStream_t);
 void launch_vocab_scatter(const float*, const long*, long, float*, long, int,
                           int, int, int, hipStream_t);
 void launch_vocab_scatter_dual(const float*, const long*, int, float*, float*,
@@ -698,6 +700,58 @@ torch::Tensor embed_grouped_scatter_bal(torch::Tensor g, torch::Tensor order,
       dtable.data_ptr<float>(), n_waves, n_waves2,
       (int)rows, (int)h, (int)g.size(1), (int)col_off, cur_stream());
   return dtable;
+}
+
+// Both P-table gradients from one pass over de [E, h]: out[:V] = dP_ifc,
+// out[V:] = dP_rpc.  The six plan tensors (int32; built and validated by
+// edge_table_plan in pertgnn/ops/functional.py) are three levels of row
+// lists: chunks of equal (ifc, rpc) key over the edges, groups over the
+// members of every over-long table row, one list per table row.  Three
+// launches of one kernel (two when there is no level 2): no memset, no
+// atomics, the final rows rounded once into out_dtype.
+torch::Tensor edge_table_grad(torch::Tensor de, torch::Tensor idx1,
+                              torch::Tensor lptr1, torch::Tensor idx2,
+                              torch::Tensor lptr2, torch::Tensor idx3,
+                              torch::Tensor lptr3, int64_t V, int64_t R,
+                              at::ScalarType out_dtype, int64_t unroll = 8) {
+  CHECK_IN(de); CHECK_IN(idx1); CHECK_IN(lptr1); CHECK_IN(idx2);
+  CHECK_IN(lptr2); CHECK_IN(idx3); CHECK_IN(lptr3);
+  TORCH_CHECK(de.dim() == 2, "de must be [E, h]");
+  TORCH_CHECK(de.scalar_type() == torch::kBFloat16 ||
+                  de.scalar_type() == torch::kFloat32,
+              "de must be bf16 or fp32");
+  TORCH_CHECK(out_dtype == torch::kBFloat16 || out_dtype == torch::kFloat32,
+              "out_dtype must be bf16 or fp32");
+  for (const auto& t : {idx1, lptr1, idx2, lptr2, idx3, lptr3})
+    TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.dim() == 1,
+                "plan tensors must be 1-D int32");
+  TORCH_CHECK(V >= 0 && R >= 0 && lptr3.numel() == V + R + 1,
+              "lptr3 must have V+R+1 entries");
+  TORCH_CHECK(lptr1.numel() >= 1 && lptr2.numel() >= 1,
+              "lptr1/lptr2 must have at least one entry");
+  TORCH_CHECK(idx1.numel() == de.size(0),
+              "level 1 must list every row of de exactly once");
+  const int h = (int)de.size(1);
+  const long n1 = lptr1.numel() - 1;
+  const long n2 = lptr2.numel() - 1;
+  const int in16 = de.scalar_type() == torch::kBFloat16 ? 1 : 0;
+  const int out16 = out_dtype == torch::kBFloat16 ? 1 : 0;
+  auto partial =
+      torch::empty({n1 + n2, (long)h}, de.options().dtype(torch::kFloat32));
+  auto out = torch::empty({V + R, (long)h}, de.options().dtype(out_dtype));
+  hipStream_t s = cur_stream();
+  launch_rows_sum_lists(de.data_ptr(), in16, idx1.data_ptr<int>(),
+                        lptr1.data_ptr<int>(), partial.data_ptr(), 0, (int)n1,
+                        h, (int)unroll, s);
+  if (n2 > 0)
+    launch_rows_sum_lists(partial.data_ptr(), 0, idx2.data_ptr<int>(),
+                          lptr2.data_ptr<int>(),
+                          partial.data_ptr<float>() + n1 * h, 0, (int)n2, h,
+                          (int)unroll, s);
+  launch_rows_sum_lists(partial.data_ptr(), 0, idx3.data_ptr<int>(),
+                        lptr3.data_ptr<int>(), out.data_ptr(), out16,
+                        (int)(V + R), h, (int)unroll, s);
+  return out;
 }
 
 std::vector<torch::Tensor> edge_attn_fused_fwd(
@@ -1380,6 +1434,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("linear_dgrad", &linear_dgrad);
   mod.def("linear_wgrad", &linear_wgrad);
   mod.def("embed_grouped_scatter_bal", &embed_grouped_scatter_bal);
+  mod.def("edge_table_grad", &edge_table_grad, py::arg("de"), py::arg("idx1"),
+          py::arg("lptr1"), py::arg("idx2"), py::arg("lptr2"),
+          py::arg("idx3"), py::arg("lptr3"), py::arg("V"), py::arg("R"),
+          py::arg("out_dtype"), py::arg("unroll") = 8);
   mod.def("bn_stats", &bn_stats);
   mod.def("bn_finalize_apply", &bn_finalize_apply, py::arg("x"),
           py::arg("partials"), py::arg("gamma"), py::arg("beta"),

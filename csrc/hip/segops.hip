@@ -402,6 +402,138 @@ void launch_embed_grouped_scatter(const float* g, const int* order,
   }
 }
 
+// ---------------------------------------------------------------------------
+// list sums: out[w, :] = sum over p in [lptr[w], lptr[w+1]) of src[idx[p], :]
+// ---------------------------------------------------------------------------
+// One wave per list, fp32 accumulation in list order (bitwise reproducible:
+// no atomics, no memset — an empty list stores a zero row).  Contiguous
+// lane*VPT column mapping with packed loads (h == VPT*64).  U rows are in
+// flight per wave: the wave index is made wave-uniform, so lptr and the U
+// idx entries are scalar loads issued ahead of the U row loads, and the
+// index-then-row dependency is paid once per U rows.  A list's last (< U)
+// rows take one more round that re-reads the last row for the unused slots
+// and adds nothing for them, so short lists keep their loads in flight too.
+// The edge-table gradient runs this three times (edge_table_grad in
+// bindings.cpp): level-1 chunks over de, level-2 groups over the partials,
+// one list per table row.
+template <int VPT, typename T>
+__device__ __forceinline__ void rows_sum_load(const T* __restrict__ row,
+                                              int lane, float (&v)[VPT]) {
+  if constexpr (sizeof(T) == 2) {
+#pragma unroll
+    for (int q = 0; q < VPT; q += 4) {
+      const segb4 x = *reinterpret_cast<const segb4*>(
+          (const __bf16*)row + lane * VPT + q);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[q + u] = (float)x[u];
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < VPT; q += 4) {
+      const segf4 x = *reinterpret_cast<const segf4*>(
+          (const float*)row + lane * VPT + q);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[q + u] = x[u];
+    }
+  }
+}
+
+template <int VPT, typename TIn, typename TOut, int U>
+__global__ void rows_sum_lists_kernel(const TIn* __restrict__ src,
+                                      const int* __restrict__ idx,
+                                      const int* __restrict__ lptr,
+                                      TOut* __restrict__ out, int n_lists) {
+  static_assert(VPT % 4 == 0, "packed loads need 4 columns per lane");
+  constexpr int H = VPT * PERTGNN_WAVE;
+  const int lane = threadIdx.x % PERTGNN_WAVE;
+  const int w = __builtin_amdgcn_readfirstlane(
+      blockIdx.x * WAVES_PER_BLOCK + threadIdx.x / PERTGNN_WAVE);
+  if (w >= n_lists) return;
+  const int p0 = lptr[w];
+  const int p1 = lptr[w + 1];
+  float acc[VPT];
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) acc[j] = 0.f;
+  int p = p0;
+  for (; p + U <= p1; p += U) {
+    int r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) r[u] = idx[p + u];
+    float v[U][VPT];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      rows_sum_load<VPT>(src + (long)r[u] * H, lane, v[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int j = 0; j < VPT; ++j) acc[j] += v[u][j];
+  }
+  if (p < p1) {
+    int r[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) r[u] = idx[min(p + u, p1 - 1)];
+    float v[U][VPT];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      rows_sum_load<VPT>(src + (long)r[u] * H, lane, v[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (p + u < p1) {
+#pragma unroll
+        for (int j = 0; j < VPT; ++j) acc[j] += v[u][j];
+      }
+  }
+  TOut* dst = out + (long)w * H + lane * VPT;
+  if constexpr (sizeof(TOut) == 2) {
+#pragma unroll
+    for (int q = 0; q < VPT; q += 4) {
+      segb4 o;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) o[u] = (__bf16)acc[q + u];
+      *reinterpret_cast<segb4*>((__bf16*)dst + q) = o;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < VPT; q += 4) {
+      segf4 o;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) o[u] = acc[q + u];
+      *reinterpret_cast<segf4*>((float*)dst + q) = o;
+    }
+  }
+}
+
+// in16/out16: bf16 rows in / out (else fp32); h in {256, 512}; unroll in
+// {4, 8}.  Only the three type pairs the edge-table gradient uses exist:
+// bf16->fp32 and fp32->fp32 (levels 1 and 2), fp32->bf16 (final rows).
+void launch_rows_sum_lists(const void* src, int in16, const int* idx,
+                           const int* lptr, void* out, int out16, int n_lists,
+                           int h, int unroll, hipStream_t s) {
+  if (n_lists == 0) return;
+  if (h != 256 && h != 512) pertgnn_shape_fail("rows_sum_lists", "h", h);
+  if (unroll != 4 && unroll != 8)
+    pertgnn_shape_fail("rows_sum_lists", "unroll", unroll);
+  if (in16 && out16) pertgnn_shape_fail("rows_sum_lists", "in16+out16", 1);
+  const dim3 block(WAVES_PER_BLOCK * PERTGNN_WAVE);
+  const dim3 grid(ceil_div(n_lists, WAVES_PER_BLOCK));
+#define RSL(V, TI, TO, UU)                                                     \
+  rows_sum_lists_kernel<V, TI, TO, UU><<<grid, block, 0, s>>>(                 \
+      (const TI*)src, idx, lptr, (TO*)out, n_lists)
+#define RSL_T(V, UU)                                                           \
+  do {                                                                         \
+    if (in16) RSL(V, __bf16, float, UU);                                       \
+    else if (out16) RSL(V, float, __bf16, UU);                                 \
+    else RSL(V, float, float, UU);                                             \
+  } while (0)
+  if (h == 256) {
+    if (unroll == 8) RSL_T(4, 8); else RSL_T(4, 4);
+  } else {
+    if (unroll == 8) RSL_T(8, 8); else RSL_T(8, 4);
+  }
+#undef RSL_T
+#undef RSL
+}
+
 // Single-pass vocab accumulator for small vocabularies: blocks stream
 // CONTIGUOUS gradient rows (coalesced, no sort/gather), accumulate into an
 // LDS-resident [V,h] table (LDS atomics — contention only within the CU),
