@@ -199,6 +199,15 @@ void launch_gemm_bf16_nn_a16(const void*, const float*, float*, int, int, int,
                              hipStream_t);
 void launch_gemm_bf16_tn_a16(const void*, const float*, float*, float*, int,
                              int, int, hipStream_t);
+// grouped P-table GEMMs (all layers, both tables, one launch each)
+int ptables_max_groups();
+void launch_ptables_fwd(int, const float* const*, const float* const*,
+                        void* const*, const int*, int, int, hipStream_t);
+void launch_ptables_dgrad(const void* const*, const float* const*, const int*,
+                          float* const*, const int*, int, int, bool,
+                          hipStream_t);
+bool launch_ptables_wgrad(int, const void* const*, const float* const*,
+                          float* const*, const int*, int, bool, hipStream_t);
 std::vector<torch::Tensor> collate_native(
     std::vector<torch::Tensor>, std::vector<torch::Tensor>,
     std::vector<torch::Tensor>, std::vector<torch::Tensor>,
@@ -1426,7 +1435,172 @@ std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
   return {dw, db};
 }
 
+// ---------------------------------------------------------------------------
+// Grouped P tables: P = table @ we^T for both embedding tables and every
+// layer in one launch; the backward in one dgrad launch (summed over layers
+// into the two table gradients) and one wgrad launch.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+// shared operand checks; returns h
+int ptables_check(const torch::Tensor& ifc_table,
+                  const torch::Tensor& rpc_table,
+                  const std::vector<torch::Tensor>& we_ifc,
+                  const std::vector<torch::Tensor>& we_rpc) {
+  CHECK_IN(ifc_table); CHECK_IN(rpc_table);
+  TORCH_CHECK(ifc_table.dim() == 2 && rpc_table.dim() == 2,
+              "ptables: tables must be 2-D");
+  TORCH_CHECK(ifc_table.scalar_type() == torch::kFloat32 &&
+                  rpc_table.scalar_type() == torch::kFloat32,
+              "ptables: tables must be float32");
+  const int64_t h = ifc_table.size(1);
+  TORCH_CHECK(h > 0 && rpc_table.size(1) == h,
+              "ptables: tables must share a non-empty hidden size");
+  TORCH_CHECK(!we_ifc.empty() && we_ifc.size() == we_rpc.size(),
+              "ptables: need one we_ifc and one we_rpc per layer, got ",
+              we_ifc.size(), " and ", we_rpc.size());
+  for (const auto* list : {&we_ifc, &we_rpc})
+    for (const auto& w : *list) {
+      TORCH_CHECK(w.is_cuda() && w.device() == ifc_table.device(),
+                  "ptables: weight must be on the tables' GPU");
+      TORCH_CHECK(w.is_contiguous(), "ptables: weight must be contiguous");
+      TORCH_CHECK(w.scalar_type() == torch::kFloat32,
+                  "ptables: weight must be float32");
+      TORCH_CHECK(w.dim() == 2 && w.size(0) == h && w.size(1) == h,
+                  "ptables: weight must be [", h, ", ", h, "]");
+    }
+  TORCH_CHECK(ifc_table.size(0) < (1 << 30) && rpc_table.size(0) < (1 << 30) &&
+                  h < (1 << 15),
+              "ptables: table too large");
+  return (int)h;
+}
+
+}  // namespace
+
+// -> [pifc_0 .. pifc_{L-1}, prpc_0 .. prpc_{L-1}], each bf16 and bit-equal to
+// linear_fwd_bf16_o16(table, we_l)
+std::vector<torch::Tensor> ptables_fwd(torch::Tensor ifc_table,
+                                       torch::Tensor rpc_table,
+                                       std::vector<torch::Tensor> we_ifc,
+                                       std::vector<torch::Tensor> we_rpc) {
+  const int h = ptables_check(ifc_table, rpc_table, we_ifc, we_rpc);
+  const int layers = (int)we_ifc.size();
+  auto opt = ifc_table.options().dtype(torch::kBFloat16);
+  std::vector<torch::Tensor> out;
+  std::vector<const float*> a, w;
+  std::vector<void*> c;
+  std::vector<int> m;
+  for (int t = 0; t < 2; ++t) {
+    const auto& table = t == 0 ? ifc_table : rpc_table;
+    const auto& ws = t == 0 ? we_ifc : we_rpc;
+    for (int l = 0; l < layers; ++l) {
+      out.push_back(torch::empty({table.size(0), h}, opt));
+      a.push_back(table.data_ptr<float>());
+      w.push_back(ws[l].data_ptr<float>());
+      c.push_back(out.back().data_ptr());
+      m.push_back((int)table.size(0));
+    }
+  }
+  launch_ptables_fwd(2 * layers, a.data(), w.data(), c.data(), m.data(), h, h,
+                     cur_stream());
+  return out;
+}
+
+// dP: 2L tensors in ptables_fwd's output order, an EMPTY tensor standing for
+// a missing (zero) gradient.  Returns (d_ifc_table [V,h], d_rpc_table [R,h],
+// dW [2L,h,h]) as views of one buffer, so one memset covers every atomic
+// accumulation; dW[g] of a missing dP[g] is zero.  dgrad_splits > 1 splits
+// the dgrad's layer sum over that many blocks (atomics; ignored under
+// PERTGNN_DETERMINISTIC=1, like the wgrad's split-K).
+std::vector<torch::Tensor> ptables_bwd(std::vector<torch::Tensor> dP,
+                                       torch::Tensor ifc_table,
+                                       torch::Tensor rpc_table,
+                                       std::vector<torch::Tensor> we_ifc,
+                                       std::vector<torch::Tensor> we_rpc,
+                                       int64_t dgrad_splits) {
+  const int h = ptables_check(ifc_table, rpc_table, we_ifc, we_rpc);
+  const int layers = (int)we_ifc.size();
+  TORCH_CHECK((int)dP.size() == 2 * layers, "ptables_bwd: need ", 2 * layers,
+              " dP entries, got ", dP.size());
+  const int64_t rows[2] = {ifc_table.size(0), rpc_table.size(0)};
+  bool missing = false;
+  for (int g = 0; g < 2 * layers; ++g) {
+    const auto& d = dP[g];
+    if (!d.defined() || d.numel() == 0) {
+      missing |= rows[g / layers] > 0;
+      continue;
+    }
+    TORCH_CHECK(d.is_cuda() && d.device() == ifc_table.device(),
+                "ptables_bwd: dP must be on the tables' GPU");
+    TORCH_CHECK(d.is_contiguous(), "ptables_bwd: dP must be contiguous");
+    TORCH_CHECK(d.scalar_type() == torch::kBFloat16,
+                "ptables_bwd: dP must be bfloat16");
+    TORCH_CHECK(d.dim() == 2 && d.size(0) == rows[g / layers] && d.size(1) == h,
+                "ptables_bwd: dP[", g, "] must be [", rows[g / layers], ", ",
+                h, "]");
+  }
+  const char* det_env = getenv("PERTGNN_DETERMINISTIC");
+  const bool det = det_env && det_env[0] == '1';
+  const int splits =
+      det ? 1 : (int)std::min<int64_t>(std::max<int64_t>(dgrad_splits, 1), layers);
+
+  const int64_t hh = (int64_t)h * h;
+  const int64_t n_dw = 2 * layers * hh;
+  auto buf = torch::empty({n_dw + (rows[0] + rows[1]) * h},
+                          ifc_table.options());
+  auto dW = buf.narrow(0, 0, n_dw).view({2 * layers, h, h});
+  auto d_ifc = buf.narrow(0, n_dw, rows[0] * h).view({rows[0], h});
+  auto d_rpc = buf.narrow(0, n_dw + rows[0] * h, rows[1] * h).view({rows[1], h});
+
+  std::vector<const void*> dp_w, dp_d;
+  std::vector<const float*> a_w, w_d;
+  std::vector<float*> dw_w;
+  std::vector<int> m_w;
+  int npairs[2] = {0, 0};
+  for (int g = 0; g < 2 * layers; ++g) {
+    const auto& d = dP[g];
+    if (!d.defined() || d.numel() == 0) continue;
+    const int t = g / layers;
+    const auto& table = t == 0 ? ifc_table : rpc_table;
+    const auto& w = (t == 0 ? we_ifc : we_rpc)[g % layers];
+    dp_w.push_back(d.data_ptr());
+    a_w.push_back(table.data_ptr<float>());
+    dw_w.push_back(dW.data_ptr<float>() + g * hh);
+    m_w.push_back((int)rows[t]);
+    dp_d.push_back(d.data_ptr());
+    w_d.push_back(w.data_ptr<float>());
+    ++npairs[t];
+  }
+  auto s = cur_stream();
+  const bool zero_dw =
+      missing || launch_ptables_wgrad((int)dp_w.size(), dp_w.data(), a_w.data(),
+                                      dw_w.data(), m_w.data(), h, true, s);
+  const bool zero_dt = splits > 1;
+  if (zero_dw || zero_dt) {
+    float* beg = buf.data_ptr<float>() + (zero_dw ? 0 : n_dw);
+    const int64_t cnt = (zero_dw ? n_dw : 0) +
+                        (zero_dt ? (rows[0] + rows[1]) * h : 0);
+    const hipError_t err = hipMemsetAsync(beg, 0, cnt * sizeof(float), s);
+    TORCH_CHECK(err == hipSuccess, "ptables_bwd: memset failed: ",
+                hipGetErrorString(err));
+  }
+  float* outs[2] = {d_ifc.data_ptr<float>(), d_rpc.data_ptr<float>()};
+  const int ms[2] = {(int)rows[0], (int)rows[1]};
+  launch_ptables_dgrad(dp_d.data(), w_d.data(), npairs, outs, ms, h, splits,
+                       zero_dt, s);
+  launch_ptables_wgrad((int)dp_w.size(), dp_w.data(), a_w.data(), dw_w.data(),
+                       m_w.data(), h, false, s);
+  return {d_ifc, d_rpc, dW};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
+  mod.def("ptables_fwd", &ptables_fwd, py::arg("ifc_table"),
+          py::arg("rpc_table"), py::arg("we_ifc"), py::arg("we_rpc"));
+  mod.def("ptables_bwd", &ptables_bwd, py::arg("dP"), py::arg("ifc_table"),
+          py::arg("rpc_table"), py::arg("we_ifc"), py::arg("we_rpc"),
+          py::arg("dgrad_splits") = 1);
+  mod.def("ptables_max_groups", &ptables_max_groups);
   mod.def("linear_fwd_bf16_o16", &linear_fwd_bf16_o16);
   mod.def("linear_dgrad16", &linear_dgrad16);
   mod.def("linear_wgrad16", &linear_wgrad16);

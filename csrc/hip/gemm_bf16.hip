@@ -224,6 +224,25 @@ struct StageCmaj {
             pack4<T16>(v[half][0][w], v[half][1][w], v[half][2][w],
                        v[half][3][w]);
   }
+
+  // what commit() rounded away: x - (float)(T16)x, itself rounded to T16.
+  // An MFMA over this image added to the one over commit()'s carries the
+  // operand to ~16 mantissa bits (grouped P-table dgrad, tiny tables).
+  __device__ __forceinline__ void commit_lo(T16* lds) const {
+    const int t = threadIdx.x;
+    const int cb = (t / FQUADS) * 4;
+    const int fq = (t % FQUADS) * 4;
+    if (SURPLUS && cb >= BK) return;
+    const auto lo = [](float x) { return x - (float)(T16)x; };
+#pragma unroll
+    for (int half = 0; half < HALVES; ++half)
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+        *reinterpret_cast<typename Vec16<T16>::v4*>(
+            &lds[(fq + w) * LDW + cb + half * CSTEP]) =
+            pack4<T16>(lo(v[half][0][w]), lo(v[half][1][w]),
+                       lo(v[half][2][w]), lo(v[half][3][w]));
+  }
 };
 
 template <int BF, int BK, typename T16, int THREADS = BGEMM_THREADS,
@@ -1448,4 +1467,399 @@ void launch_gemm_skinny_nn(const void* g_v, const float* w, float* dx, int m,
   gemm_skinny_nn_kernel<<<dim3(m, (k2 + PERTGNN_WAVE - 1) / PERTGNN_WAVE),
                           dim3(PERTGNN_WAVE), 0, s>>>(
       (const __bf16*)g_v, w, dx, m, n, k2);
+}
+
+// ---------------------------------------------------------------------------
+// Grouped P-table GEMMs.  Every layer projects the same two embedding tables
+// (interface [V,H], rpctype [R,H]) through its own [H,H] edge weights; run
+// per layer these are 4-32-block launches that leave most of the chip idle.
+// The three kernels below take ALL layers' operands in one launch: the group
+// is found from blockIdx, and the per-group pointers and row counts arrive
+// in a descriptor struct passed BY VALUE (kernarg: no device pointer array,
+// no host-to-device copy, and a captured graph bakes the addresses in).  A
+// struct holds at most PT_MAX_GROUPS groups; the launchers split above that.
+//
+// All three use the 64x64x64 register-staging tile of the small-shape
+// kernels above (36 KB LDS, 4 blocks/CU; 45 KB and 3 in the dgrad).  A
+// block's result depends only on its operands and the ascending order of
+// its 32-wide MFMA K steps, never on the grid, so the forward is
+// bit-identical to the per-layer gemm_bf16_nt_kernel launches whatever tile
+// those picked.
+// ---------------------------------------------------------------------------
+
+#define PT_MAX_GROUPS 32
+#define PT_TILE 64
+
+struct PTFwdArgs {
+  const float* a[PT_MAX_GROUPS];   // table [m_g, k]
+  const float* w[PT_MAX_GROUPS];   // weight [n, k]
+  __bf16* c[PT_MAX_GROUPS];        // out [m_g, n]
+  int m[PT_MAX_GROUPS];
+  int blk_beg[PT_MAX_GROUPS + 1];  // first block of each group
+  int groups, n, k;
+};
+
+// C_g (bf16) = A_g (fp32) @ W_g^T (fp32), heterogeneous m_g
+__launch_bounds__(BGEMM_THREADS)
+__global__ void ptables_fwd_kernel(const PTFwdArgs p) {
+  constexpr int BM = PT_TILE, BN = PT_TILE, BK = 64;
+  constexpr int LDW = BK + BGEMM_PAD;
+  constexpr int WCOL = BGEMM_THREADS / PERTGNN_WAVE / 2;
+  constexpr int FM = (BM / 2) / 16, FN = (BN / WCOL) / 16;
+  __shared__ __bf16 lds_a[2][BM * LDW];
+  __shared__ __bf16 lds_b[2][BN * LDW];
+  const int bid = blockIdx.x;
+  int g = 0;
+  while (g + 1 < p.groups && bid >= p.blk_beg[g + 1]) ++g;
+  const float* __restrict__ a = p.a[g];
+  const float* __restrict__ b = p.w[g];
+  const int m = p.m[g], n = p.n, k = p.k;
+  const int tile = bid - p.blk_beg[g];
+  const int tiles_n = (n + BN - 1) / BN;
+  const int m0 = (tile / tiles_n) * BM;
+  const int n0 = (tile % tiles_n) * BN;
+  const int wave = threadIdx.x / PERTGNN_WAVE;
+  const int lane = threadIdx.x % PERTGNN_WAVE;
+  const int wm = (wave / WCOL) * (BM / 2);
+  const int wn = (wave % WCOL) * (BN / WCOL);
+
+  BWaveTile<FM, FN, BK, __bf16> wt;
+  wt.zero();
+  int buf = 0;
+  bstage_cmin<BM, BK, __bf16>(a, k, m0, 0, m, k, lds_a[0]);
+  bstage_cmin<BN, BK, __bf16>(b, k, n0, 0, n, k, lds_b[0]);
+  __syncthreads();
+  StageCmin<BM, BK, __bf16, float> sa;
+  StageCmin<BN, BK, __bf16, float> sb;
+  for (int k0 = BK; k0 < k; k0 += BK) {
+    sa.load(a, k, m0, k0, m, k);
+    sb.load(b, k, n0, k0, n, k);
+    wt.mma(lds_a[buf], lds_b[buf], wm, wn, lane);
+    sa.commit(lds_a[buf ^ 1]);
+    sb.commit(lds_b[buf ^ 1]);
+    __syncthreads();
+    buf ^= 1;
+  }
+  wt.mma(lds_a[buf], lds_b[buf], wm, wn, lane);
+  wt.store(p.c[g], n, m0 + wm, n0 + wn, m, n, nullptr, 0, lane);
+}
+
+struct PTDgradArgs {
+  const __bf16* dp[PT_MAX_GROUPS];  // (dP_l, W_l) pairs, table 0's first
+  const float* w[PT_MAX_GROUPS];
+  int pair_beg[3];                  // table t owns pairs [beg[t], beg[t+1])
+  float* out[2];                    // dT_t [m_t, h]
+  int m[2];
+  int blk_beg[3];
+  int h;
+  int splits;   // >1: each block takes 1/splits of its table's pairs
+  int atomic;   // add into out (zeroed, or holding an earlier launch's sum)
+};
+
+// dT_t (fp32) = sum_l dP_l (bf16) @ W_l (fp32) for both tables: the K loop
+// walks the table's (dP_l, W_l) pairs — one GEMM with K = L*h — so the
+// per-layer dgrads and the L-1 adds of their results become one register
+// accumulation in a fixed order (or, with `splits`, a few atomic partials).
+__launch_bounds__(BGEMM_THREADS)
+__global__ void ptables_dgrad_kernel(const PTDgradArgs p) {
+  constexpr int BM = PT_TILE, BN = PT_TILE, BK = 64;
+  constexpr int LDW = BK + BGEMM_PAD;
+  constexpr int WCOL = BGEMM_THREADS / PERTGNN_WAVE / 2;
+  constexpr int FM = (BM / 2) / 16, FN = (BN / WCOL) / 16;
+  __shared__ __bf16 lds_a[2][BM * LDW];
+  __shared__ __bf16 lds_b[2][BN * LDW];
+  __shared__ __bf16 lds_b_lo[BN * LDW];  // single buffer: 45 KB, 3 blocks/CU
+  const int bid = blockIdx.x;
+  const int t = bid >= p.blk_beg[1] ? 1 : 0;
+  const int m = p.m[t], h = p.h;
+  // Tables of at most 16 rows (rpctype) keep the low half of the fp32
+  // weights in a second B image and run a second MFMA over it: their
+  // per-layer dgrad is the skinny fp32-FMA kernel, which never rounded W,
+  // and a bf16-rounded W here would move that gradient by 2^-9 relative
+  // (1e-5 at the flagship) where two runs of one tree differ by 1e-8.
+  const bool exact_w = m <= 16;
+  const int tiles_n = (h + BN - 1) / BN;
+  const int tiles = ((m + BM - 1) / BM) * tiles_n;
+  const int rel = bid - p.blk_beg[t];
+  const int split = rel / tiles;
+  const int tile = rel % tiles;
+  const int m0 = (tile / tiles_n) * BM;
+  const int n0 = (tile % tiles_n) * BN;
+  const int wave = threadIdx.x / PERTGNN_WAVE;
+  const int lane = threadIdx.x % PERTGNN_WAVE;
+  const int wm = (wave / WCOL) * (BM / 2);
+  const int wn = (wave % WCOL) * (BN / WCOL);
+
+  const int npairs = p.pair_beg[t + 1] - p.pair_beg[t];
+  const int per = (npairs + p.splits - 1) / p.splits;
+  const int l_beg = p.pair_beg[t] + min(npairs, split * per);
+  const int l_end = p.pair_beg[t] + min(npairs, (split + 1) * per);
+  // an atomic block with no pairs adds nothing; a storing one writes zeros
+  if (p.atomic && l_beg >= l_end) return;
+
+  // Two-level sum: each pair's K = h chain runs in the MFMA accumulator from
+  // zero, exactly as its per-layer dgrad would, and is then added to `tot`
+  // with one fp32 add.  One chain over all L*h was measured 3x less accurate
+  // than the per-layer path at L = 3, h = 256 (3.1e-6 vs 1.1e-6 on outputs
+  // of 7): every MFMA step rounds at the magnitude of the running sum.
+  BWaveTile<FM, FN, BK, __bf16> wt;
+  f32x4 tot[FM][FN];
+  wt.zero();
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j) tot[i][j] = {0.f, 0.f, 0.f, 0.f};
+  if (l_beg < l_end) {
+    int buf = 0;
+    int l = l_beg, c0 = 0;  // the K step staged in lds[buf]
+    StageCmin<BM, BK, __bf16, __bf16> sa;
+    StageCmaj<BN, BK, __bf16, float> sb;
+    bstage_cmin<BM, BK, __bf16>(p.dp[l], h, m0, 0, m, h, lds_a[0]);
+    sb.load(p.w[l], h, 0, n0, h, h);
+    sb.commit(lds_b[0]);
+    if (exact_w) sb.commit_lo(lds_b_lo);
+    __syncthreads();
+    while (true) {
+      int nl = l, nc = c0 + BK;
+      if (nc >= h) { nc = 0; ++nl; }
+      const bool more = nl < l_end;
+      if (more) {
+        sa.load(p.dp[nl], h, m0, nc, m, h);
+        sb.load(p.w[nl], h, nc, n0, h, h);
+      }
+      wt.mma(lds_a[buf], lds_b[buf], wm, wn, lane);
+      if (exact_w) wt.mma(lds_a[buf], lds_b_lo, wm, wn, lane);
+      if (nc == 0) {  // that was pair l's last step
+#pragma unroll
+        for (int i = 0; i < FM; ++i)
+#pragma unroll
+          for (int j = 0; j < FN; ++j) {
+            tot[i][j] += wt.acc[i][j];
+            wt.acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+          }
+      }
+      if (!more) break;
+      sa.commit(lds_a[buf ^ 1]);
+      sb.commit(lds_b[buf ^ 1]);
+      if (exact_w) {  // every wave is done reading the one lo image
+        __syncthreads();
+        sb.commit_lo(lds_b_lo);
+      }
+      __syncthreads();
+      buf ^= 1;
+      l = nl;
+      c0 = nc;
+    }
+  }
+
+  float* __restrict__ c = p.out[t];
+  const int fcol = lane & 15;
+  const int frow = (lane >> 4) * 4;
+#pragma unroll
+  for (int mi = 0; mi < FM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < FN; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = m0 + wm + mi * 16 + frow + r;
+        const int col = n0 + wn + ni * 16 + fcol;
+        if (row < m && col < h) {
+          if (p.atomic)
+            atomicAdd(&c[(long)row * h + col], tot[mi][ni][r]);
+          else
+            c[(long)row * h + col] = tot[mi][ni][r];
+        }
+      }
+}
+
+struct PTWgradArgs {
+  const __bf16* dp[PT_MAX_GROUPS];  // dP_g [m_g, h]
+  const float* a[PT_MAX_GROUPS];    // table [m_g, h]
+  float* dw[PT_MAX_GROUPS];         // dW_g [h, h]
+  int m[PT_MAX_GROUPS];
+  int slices[PT_MAX_GROUPS];        // split-K over m_g; >1 adds atomically
+  int blk_beg[PT_MAX_GROUPS + 1];
+  int groups, h;
+};
+
+// dW_g (fp32) = dP_g^T (bf16) @ A_g (fp32), reducing over m_g
+__launch_bounds__(BGEMM_THREADS)
+__global__ void ptables_wgrad_kernel(const PTWgradArgs p) {
+  constexpr int BM = PT_TILE, BN = PT_TILE, BK = 64;
+  constexpr int LDW = BK + BGEMM_PAD;
+  constexpr int WCOL = BGEMM_THREADS / PERTGNN_WAVE / 2;
+  constexpr int FM = (BM / 2) / 16, FN = (BN / WCOL) / 16;
+  __shared__ __bf16 lds_a[2][BM * LDW];
+  __shared__ __bf16 lds_b[2][BN * LDW];
+  const int bid = blockIdx.x;
+  int g = 0;
+  while (g + 1 < p.groups && bid >= p.blk_beg[g + 1]) ++g;
+  const __bf16* __restrict__ a = p.dp[g];
+  const float* __restrict__ b = p.a[g];
+  const int m = p.m[g], h = p.h, slices = p.slices[g];
+  const int rel = bid - p.blk_beg[g];
+  const int tiles_k = (h + BN - 1) / BN;
+  const int tile_id = rel / slices;
+  const int slice = rel % slices;
+  const int n0 = (tile_id / tiles_k) * BM;
+  const int k0 = (tile_id % tiles_k) * BN;
+  const int wave = threadIdx.x / PERTGNN_WAVE;
+  const int lane = threadIdx.x % PERTGNN_WAVE;
+  const int wm = (wave / WCOL) * (BM / 2);
+  const int wn = (wave % WCOL) * (BN / WCOL);
+
+  const int per_slice = ((m + slices - 1) / slices + BK - 1) / BK * BK;
+  const int c_beg = slice * per_slice;
+  const int c_end = min(m, c_beg + per_slice);
+  if (slices > 1 && c_beg >= c_end) return;
+
+  BWaveTile<FM, FN, BK, __bf16> wt;
+  wt.zero();
+  if (c_beg < c_end) {
+    int buf = 0;
+    bstage_cmaj<BM, BK, __bf16>(a, h, c_beg, n0, c_end, h, lds_a[0]);
+    bstage_cmaj<BN, BK, __bf16>(b, h, c_beg, k0, c_end, h, lds_b[0]);
+    __syncthreads();
+    StageCmaj<BM, BK, __bf16, __bf16> sa;
+    StageCmaj<BN, BK, __bf16, float> sb;
+    for (int cc = c_beg + BK; cc < c_end; cc += BK) {
+      sa.load(a, h, cc, n0, c_end, h);
+      sb.load(b, h, cc, k0, c_end, h);
+      wt.mma(lds_a[buf], lds_b[buf], wm, wn, lane);
+      sa.commit(lds_a[buf ^ 1]);
+      sb.commit(lds_b[buf ^ 1]);
+      __syncthreads();
+      buf ^= 1;
+    }
+    wt.mma(lds_a[buf], lds_b[buf], wm, wn, lane);
+  }
+
+  float* __restrict__ c = p.dw[g];
+  const int fcol = lane & 15;
+  const int frow = (lane >> 4) * 4;
+#pragma unroll
+  for (int mi = 0; mi < FM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < FN; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = n0 + wm + mi * 16 + frow + r;
+        const int col = k0 + wn + ni * 16 + fcol;
+        if (row < h && col < h) {
+          if (slices == 1)
+            c[(long)row * h + col] = wt.acc[mi][ni][r];
+          else
+            atomicAdd(&c[(long)row * h + col], wt.acc[mi][ni][r]);
+        }
+      }
+}
+
+int ptables_max_groups() { return PT_MAX_GROUPS; }
+
+static inline int pt_tiles(int rows, int cols) {
+  return ((rows + PT_TILE - 1) / PT_TILE) * ((cols + PT_TILE - 1) / PT_TILE);
+}
+
+// forward: groups = every (table, layer) product; m[g] rows, all [.,k]x[n,k]^T
+void launch_ptables_fwd(int groups, const float* const* a,
+                        const float* const* w, void* const* c, const int* m,
+                        int n, int k, hipStream_t s) {
+  for (int g0 = 0; g0 < groups; g0 += PT_MAX_GROUPS) {
+    PTFwdArgs p;
+    p.groups = min(PT_MAX_GROUPS, groups - g0);
+    p.n = n;
+    p.k = k;
+    int blocks = 0;
+    for (int i = 0; i < p.groups; ++i) {
+      p.a[i] = a[g0 + i];
+      p.w[i] = w[g0 + i];
+      p.c[i] = (__bf16*)c[g0 + i];
+      p.m[i] = m[g0 + i];
+      p.blk_beg[i] = blocks;
+      blocks += pt_tiles(m[g0 + i], n);
+    }
+    p.blk_beg[p.groups] = blocks;
+    if (blocks > 0)
+      ptables_fwd_kernel<<<dim3(blocks), dim3(BGEMM_THREADS), 0, s>>>(p);
+  }
+}
+
+// table dgrad: npairs[t] (dP, W) pairs per table, table 0's first in dp/w.
+// Writes out[t] [m[t], h] unless `zeroed` (the caller cleared both outputs),
+// in which case every launch adds atomically and `splits` may exceed 1.
+// Without `zeroed` the sum order is fixed: launches past the first (more
+// pairs than one struct holds) add onto the stored result in stream order,
+// one block per element.
+void launch_ptables_dgrad(const void* const* dp, const float* const* w,
+                          const int* npairs, float* const* out, const int* m,
+                          int h, int splits, bool zeroed, hipStream_t s) {
+  if (!zeroed) splits = 1;
+  const int half = PT_MAX_GROUPS / 2;  // pairs per table per launch
+  const int most = max(npairs[0], npairs[1]);
+  bool first = true;
+  for (int l0 = 0; l0 < most || first; l0 += half) {
+    PTDgradArgs p;
+    int np = 0, blocks = 0;
+    for (int t = 0; t < 2; ++t) {
+      const int base = t == 0 ? 0 : npairs[0];
+      const int cnt = max(0, min(half, npairs[t] - l0));
+      p.pair_beg[t] = np;
+      for (int i = 0; i < cnt; ++i) {
+        p.dp[np] = (const __bf16*)dp[base + l0 + i];
+        p.w[np] = w[base + l0 + i];
+        ++np;
+      }
+      p.out[t] = out[t];
+      p.m[t] = m[t];
+      p.blk_beg[t] = blocks;
+      // a table with nothing (more) to add needs blocks only to store zeros
+      if (cnt > 0 || (first && !zeroed)) blocks += pt_tiles(m[t], h) * splits;
+    }
+    p.pair_beg[2] = np;
+    p.blk_beg[2] = blocks;
+    p.h = h;
+    p.splits = splits;
+    p.atomic = (zeroed || !first) ? 1 : 0;
+    if (blocks > 0)
+      ptables_dgrad_kernel<<<dim3(blocks), dim3(BGEMM_THREADS), 0, s>>>(p);
+    first = false;
+  }
+}
+
+// weight wgrad: dw[g] [h,h] = dp[g]^T @ a[g] over m[g] rows.  Outside
+// PERTGNN_DETERMINISTIC=1 large-m groups are split-K'd with atomics, and the
+// caller must then have zeroed every dw (returns true if it relies on that);
+// `probe` only answers that question without launching.
+bool launch_ptables_wgrad(int groups, const void* const* dp,
+                          const float* const* a, float* const* dw,
+                          const int* m, int h, bool probe, hipStream_t s) {
+  const bool det = pertgnn_deterministic();
+  int total_tiles = 0;
+  for (int g = 0; g < groups; ++g) total_tiles += pt_tiles(h, h);
+  bool any_split = false;
+  for (int g0 = 0; g0 < groups; g0 += PT_MAX_GROUPS) {
+    PTWgradArgs p;
+    p.groups = min(PT_MAX_GROUPS, groups - g0);
+    p.h = h;
+    int blocks = 0;
+    for (int i = 0; i < p.groups; ++i) {
+      const int mg = m[g0 + i];
+      int slices = 1;
+      while (!det && (long)total_tiles * slices < 2048 && slices < 64 &&
+             (long)slices * 64 * 4 < mg)
+        slices *= 2;
+      any_split |= slices > 1;
+      p.dp[i] = (const __bf16*)dp[g0 + i];
+      p.a[i] = a[g0 + i];
+      p.dw[i] = dw[g0 + i];
+      p.m[i] = mg;
+      p.slices[i] = slices;
+      p.blk_beg[i] = blocks;
+      blocks += pt_tiles(h, h) * slices;
+    }
+    p.blk_beg[p.groups] = blocks;
+    if (!probe && blocks > 0)
+      ptables_wgrad_kernel<<<dim3(blocks), dim3(BGEMM_THREADS), 0, s>>>(p);
+  }
+  return any_split;
 }

@@ -211,12 +211,14 @@ class TransformerConv(nn.Module):
                                   heads=self.heads)
 
     def forward_fused(self, x, edge_attr, ifc_weight, rpc_weight, csr,
-                      out16=False):
+                      out16=False, pifc=None, prpc=None):
         """HIP fast path: one [N,K]x[4H,K]^T GEMM for q/k/v/skip and
         L2-resident per-vocab P tables instead of the [E,2H] edge-embed
         stream (exact refactoring by linearity of lin_edge).  In bf16/fp16
         precision with H%256==0 the qkvs tensor is kept bf16-resident
-        through the attention kernels."""
+        through the attention kernels.  ``pifc`` / ``prpc``: this layer's
+        bf16 P tables when the caller computed all layers' at once
+        (``ops.ptables_grouped``); without them they are computed here."""
         h = self.out_channels
         # w4/b4 ARE the parameters (no per-step cat); the storage is
         # pre-padded to k_padded with zero columns (zero-grad columns stay
@@ -228,7 +230,9 @@ class TransformerConv(nn.Module):
                  and ops.act16_enabled())
         if act16:
             qkvs = ops.linear16(x, self.w4, self.b4)
-            if ops.p16_enabled():
+            if pifc is not None and prpc is not None:
+                pass  # grouped: computed once for all layers by the caller
+            elif ops.p16_enabled():
                 # bf16 P tables: halves the per-edge ec gather bytes AND the
                 # L2 footprint of the tables (2x256H fp32 = 4 MB at realistic
                 # vocab vs 4 MB L2 per XCD); logits/softmax stay fp32
@@ -353,11 +357,24 @@ class SAGEDeterministic(nn.Module):
             )
         n = x.shape[0]
 
+        # the embedding tables do not change inside a step: with bf16 P
+        # tables, all layers' table @ we^T products (and their backward) run
+        # as grouped launches instead of per layer
+        ptables = {}
+        if out16 and ops.p16_enabled() and ops.ptable_group_enabled():
+            pifcs, prpcs = ops.ptables_grouped(
+                self.interface_embeds.weight, self.rpctype_embeds.weight,
+                [c.we_ifc for c in self.convs], [c.we_rpc for c in self.convs])
+            ptables = {id(c): pair
+                       for c, pair in zip(self.convs, zip(pifcs, prpcs))}
+
         def run_conv(conv, x, out16=False):
             if fused:
+                pifc, prpc = ptables.get(id(conv), (None, None))
                 return conv.forward_fused(
                     x, edge_attr, self.interface_embeds.weight,
                     self.rpctype_embeds.weight, csr, out16=out16,
+                    pifc=pifc, prpc=prpc,
                 )
             return conv(x, edge_index, edge_embeds, csr=csr, num_nodes=n)
 

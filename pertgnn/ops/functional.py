@@ -426,6 +426,61 @@ def linear16(x, w, b=None):
     return _Linear16Fn.apply(x, w, b)
 
 
+class _PTablesFn(torch.autograd.Function):
+    """All layers' bf16 P tables (``linear16(table, we_l)`` for both embedding
+    tables) in one grouped launch.  The 2L tables are separate outputs, so
+    autograd hands the backward every ``dP`` at once, after the first layer's
+    attention backward: one dgrad launch sums over the layers into the two
+    table gradients and one wgrad launch fills all 2L weight gradients."""
+
+    @staticmethod
+    def forward(ctx, ifc_table, rpc_table, *weights):
+        layers = len(weights) // 2
+        we_ifc, we_rpc = list(weights[:layers]), list(weights[layers:])
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(ifc_table, rpc_table, *weights)
+        return tuple(ext().ptables_fwd(ifc_table, rpc_table, we_ifc, we_rpc))
+
+    @staticmethod
+    def backward(ctx, *dps):
+        ifc_table, rpc_table, *weights = ctx.saved_tensors
+        layers = len(weights) // 2
+        none = torch.empty(0, dtype=torch.bfloat16, device=ifc_table.device)
+        d_ifc, d_rpc, dw = ext().ptables_bwd(
+            [none if g is None else g.contiguous() for g in dps],
+            ifc_table, rpc_table, weights[:layers], weights[layers:],
+            ptable_dgrad_splits())
+        return (d_ifc, d_rpc,
+                *(None if g is None else dw[i] for i, g in enumerate(dps)))
+
+
+def ptables_grouped(ifc_table, rpc_table, we_ifc, we_rpc):
+    """-> ([pifc_l], [prpc_l]): bf16, each bit-equal to ``linear16(table,
+    we_l)``; ``we_ifc`` / ``we_rpc`` are the per-layer [H,H] weights."""
+    if len(we_ifc) != len(we_rpc):
+        raise ValueError(f"{len(we_ifc)} we_ifc vs {len(we_rpc)} we_rpc")
+    layers = len(we_ifc)
+    out = _PTablesFn.apply(ifc_table, rpc_table, *we_ifc, *we_rpc)
+    return list(out[:layers]), list(out[layers:])
+
+
+def ptable_group_enabled() -> bool:
+    """Grouped P-table GEMMs (PERTGNN_NO_PTABLE_GROUP=1 keeps the per-layer
+    launches; read per call so one process can run both for comparison)."""
+    import os
+    return os.environ.get("PERTGNN_NO_PTABLE_GROUP", "0") != "1"
+
+
+def ptable_dgrad_splits() -> int:
+    """Blocks sharing one output tile's layer sum in the grouped table dgrad
+    (PERTGNN_PTABLE_DGRAD_SPLIT, default 4: 98 -> 55 us for the whole
+    backward at 8 layers, profiles/16; >1 adds atomically into the memset
+    buffer and is ignored under PERTGNN_DETERMINISTIC=1; never more than the
+    layer count)."""
+    import os
+    return int(os.environ.get("PERTGNN_PTABLE_DGRAD_SPLIT", "4"))
+
+
 _ACT16 = None
 _P16 = None
 
@@ -1011,6 +1066,8 @@ __all__ = [
     "p16_enabled",
     "gemm_precision",
     "linear16",
+    "ptables_grouped",
+    "ptable_group_enabled",
     "act16_enabled",
     "edge_attention",
     "edge_attention_fused",
