@@ -3,8 +3,11 @@
 #include <torch/extension.h>
 
 #include <cstdlib>
+#include <optional>
 
 #include <c10/cuda/CUDAStream.h>
+
+#include "hip/attn_bn.h"
 
 namespace {
 
@@ -172,7 +175,11 @@ void launch_edge_attn_fused_bwd16(const void*, int, const void*,
                                   int, const float*, const int*, const int*,
                                   const int*, const int*, const int*, void*,
                                   void*, float*, int, int, long, int,
-                                  hipStream_t);
+                                  hipStream_t, const AttnBnBwd* = nullptr);
+void launch_bn_bwd_partials_affine16(const void*, const void*,
+                                     const unsigned char*, const float*,
+                                     const float*, long, int, float*, float,
+                                     float*, float*, float*, hipStream_t);
 void launch_edge_attn_fused_infer(const float*, const float*, const float*,
                                   const long*, int, const int*, const int*,
                                   const float*, const float*, int, float*,
@@ -1300,6 +1307,107 @@ std::vector<torch::Tensor> bn_bwd_apply16(
   return {dx, dgamma, dbeta};
 }
 
+// Backward of "fused attention forward -> BN+ReLU(+dropout) forward" in act16
+// mode: g is the gradient of the BN output, x the attention output the BN
+// read, mask the BN forward's keep mask.  The BN partials run as in
+// bn_relu_bwd16; the element-wise BN backward runs inside the attention
+// backward's row kernel, so no [n, h] dx is allocated, written or re-read.
+// Sync-BN passes the all-reduced [2h+1] partials (global count in the tail
+// slot) and the local [2h+1] ones (dgamma/dbeta), as bn_bwd_apply16 takes
+// them.  Returns {dqkvs, de, dgamma, dbeta}.
+std::vector<torch::Tensor> edge_attn_bn_bwd16(
+    torch::Tensor g, torch::Tensor x, torch::Tensor mask, torch::Tensor gamma,
+    torch::Tensor mean, torch::Tensor invstd, double keep_inv,
+    torch::Tensor qkvs, torch::Tensor pifc, torch::Tensor prpc,
+    torch::Tensor ea, torch::Tensor alpha, torch::Tensor row_ptr,
+    torch::Tensor csr_src, torch::Tensor col_ptr, torch::Tensor csc_dst,
+    torch::Tensor csc_eid, int64_t heads = 1,
+    std::optional<torch::Tensor> partials_global_opt = std::nullopt,
+    std::optional<torch::Tensor> partials_local_opt = std::nullopt) {
+  CHECK_IN(g); CHECK_IN(x); CHECK_IN(qkvs); CHECK_IN(alpha); CHECK_IN(mask);
+  CHECK_IN(gamma); CHECK_IN(mean); CHECK_IN(invstd);
+  const int n = qkvs.size(0);
+  const int h = qkvs.size(1) / 4;
+  const long ne = ea.size(0);
+  TORCH_CHECK(n > 0, "edge_attn_bn_bwd16 needs at least one node");
+  TORCH_CHECK(h == 256 || h == 512, "edge_attn_bn_bwd16 covers H = 256, 512");
+  TORCH_CHECK(qkvs.scalar_type() == torch::kBFloat16 &&
+                  g.scalar_type() == torch::kBFloat16 &&
+                  x.scalar_type() == torch::kBFloat16,
+              "edge_attn_bn_bwd16 takes bf16 qkvs, g and x");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == n && x.size(1) == h &&
+                  g.sizes() == x.sizes(),
+              "g and x must be [n, h]");
+  TORCH_CHECK(mask.scalar_type() == torch::kUInt8,
+              "edge_attn_bn_bwd16 needs the BN forward's keep mask");
+  TORCH_CHECK(gamma.numel() == h && mean.numel() == h && invstd.numel() == h &&
+                  gamma.scalar_type() == torch::kFloat32 &&
+                  mean.scalar_type() == torch::kFloat32 &&
+                  invstd.scalar_type() == torch::kFloat32,
+              "gamma/mean/invstd must be fp32 [h]");
+  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
+              "heads must divide H (H=", h, ", heads=", heads, ")");
+  TORCH_CHECK(alpha.scalar_type() == torch::kFloat32 &&
+                  alpha.numel() == ne * heads,
+              "alpha must be the fp32 [E, heads] tensor of the forward");
+  TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(),
+              "P tables must share a dtype");
+  const bool sync = partials_global_opt.has_value();
+  TORCH_CHECK(sync == partials_local_opt.has_value(),
+              "partials_global and partials_local come together");
+  torch::Tensor partials_global, partials_local;
+  if (sync) {
+    partials_global = *partials_global_opt;
+    partials_local = *partials_local_opt;
+  }
+  auto fopt = qkvs.options().dtype(torch::kFloat32);
+  auto dgamma = torch::empty({h}, fopt);
+  auto dbeta = torch::empty({h}, fopt);
+  AttnBnBwd bn{};
+  bn.x = x.data_ptr();
+  bn.mask = bn_mask_ptr(mask, x);
+  bn.mean = mean.data_ptr<float>();
+  bn.invstd = invstd.data_ptr<float>();
+  bn.gamma = gamma.data_ptr<float>();
+  bn.count = n;
+  bn.keep_inv = (float)keep_inv;
+  torch::Tensor partials, slab;  // alive until the launches are queued
+  if (sync) {
+    CHECK_IN(partials_global); CHECK_IN(partials_local);
+    TORCH_CHECK(partials_global.numel() == 2 * h + 1 &&
+                    partials_local.numel() >= 2 * h &&
+                    partials_global.scalar_type() == torch::kFloat32 &&
+                    partials_local.scalar_type() == torch::kFloat32,
+                "edge_attn_bn_bwd16 expects fp32 [2h+1] partials with the "
+                "global count in the tail slot");
+    bn.partials = partials_global.data_ptr<float>();
+    bn.count_ptr = partials_global.data_ptr<float>() + 2 * h;
+    launch_bn_grad_affine(partials_local.data_ptr<float>(),
+                          dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), h,
+                          cur_stream());
+  } else {
+    partials = torch::empty({2 * h}, fopt);
+    slab = bn_wide_slab(x);
+    launch_bn_bwd_partials_affine16(
+        g.data_ptr(), x.data_ptr(), bn.mask, bn.mean, bn.invstd, n, h,
+        partials.data_ptr<float>(), bn.keep_inv, bn_slab_ptr(slab),
+        dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), cur_stream());
+    bn.partials = partials.data_ptr<float>();
+  }
+  auto dqkvs = torch::empty_like(qkvs);
+  auto de = torch::empty({ne, h}, qkvs.options());
+  auto dal = torch::empty({ne * heads}, fopt);
+  const int p16 = pifc.scalar_type() == torch::kBFloat16 ? 1 : 0;
+  launch_edge_attn_fused_bwd16(
+      g.data_ptr(), 1, qkvs.data_ptr(), pifc.data_ptr(), prpc.data_ptr(), p16,
+      ea.data_ptr<long>(), (int)ea.size(1), alpha.data_ptr<float>(),
+      row_ptr.data_ptr<int>(), csr_src.data_ptr<int>(),
+      col_ptr.data_ptr<int>(), csc_dst.data_ptr<int>(),
+      csc_eid.data_ptr<int>(), dqkvs.data_ptr(), de.data_ptr(),
+      dal.data_ptr<float>(), n, h, ne, (int)heads, cur_stream(), &bn);
+  return {dqkvs, de, dgamma, dbeta};
+}
+
 torch::Tensor seg_pool_fwd16(torch::Tensor x, torch::Tensor probs,
                              torch::Tensor nn, torch::Tensor batch_ptr,
                              int64_t num_graphs) {
@@ -1682,6 +1790,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
           py::arg("partials_global"), py::arg("partials_local"),
           py::arg("relu"), py::arg("keep_inv") = 1.0);
+  mod.def("edge_attn_bn_bwd16", &edge_attn_bn_bwd16, py::arg("g"),
+          py::arg("x"), py::arg("mask"), py::arg("gamma"), py::arg("mean"),
+          py::arg("invstd"), py::arg("keep_inv"), py::arg("qkvs"),
+          py::arg("pifc"), py::arg("prpc"), py::arg("edge_attr"),
+          py::arg("alpha"), py::arg("row_ptr"), py::arg("csr_src"),
+          py::arg("col_ptr"), py::arg("csc_dst"), py::arg("csc_eid"),
+          py::arg("heads") = 1, py::arg("partials_global") = py::none(),
+          py::arg("partials_local") = py::none());
   mod.def("seg_pool_fwd16", &seg_pool_fwd16);
   mod.def("seg_pool_bwd16", &seg_pool_bwd16);
   mod.def("linear_fwd_a16o16", &linear_fwd_a16o16, py::arg("x"), py::arg("w"),

@@ -50,6 +50,22 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
   return v;
 }
 
+// One element of the training BN(+ReLU+dropout) backward, rounded to bf16 as
+// the dx store rounds it: g = output gradient, keep = the element's keep-mask
+// bit, p0/p1 = per-channel sums of gm and gm*xhat, invn = 1/rows.  The
+// contraction is pinned (one fma, every other step rounded on its own), so
+// every kernel that inlines this gives the same bits for the same inputs.
+__device__ __forceinline__ __bf16 bn_bwd_dx16(float g, float x, bool keep,
+                                              float mu, float is, float ga,
+                                              float p0, float p1, float invn,
+                                              float keep_inv) {
+#pragma clang fp contract(off)
+  const float gm = keep ? g * keep_inv : 0.f;
+  const float xhat = (x - mu) * is;
+  return (__bf16)((ga * is) *
+                  __builtin_fmaf(-invn, xhat * p1, gm - p0 * invn));
+}
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // XCD-aware blockIdx remap (guide §5.5 T1, bijective form): the dispatcher

@@ -26,8 +26,10 @@
 // dP_ifc/dP_rpc.  Deterministic — no atomics anywhere.
 
 #include "common.h"
+#include "attn_bn.h"
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
 #define WAVES_PER_BLOCK 4
 
@@ -427,6 +429,43 @@ __global__ void edge_attn_fused_infer_kernel(
   S::store(&out[(long)row * h], lane, h, res);
 }
 
+// BN(+ReLU+dropout) backward of one row slice in the VEC mapping: gr holds
+// the BN output gradient of the lane's VPT contiguous channels on entry and
+// the BN input gradient, rounded to bf16, on return — the bits the stand-
+// alone bn_bwd_apply_wide_kernel stores as dx.  Keep-mask layout (segops.hip,
+// above bn_wide_ok): bit u of byte (r, c/8) belongs to channel c+u, so the
+// lane's bits start at bit (lane*VPT)%8 of byte (lane*VPT)/8 of the row's
+// h/8 bytes (VPT = 4 shares a byte between two lanes, VPT >= 8 owns VPT/8
+// bytes).  The per-channel constants are live in here only.
+template <int VPT>
+__device__ __forceinline__ void attn_bn_bwd_row(const AttnBnBwd& bn, int row,
+                                                int lane, int h,
+                                                float (&gr)[VPT]) {
+  using S = Slice<VPT, true>;
+  static_assert(VPT == 4 || VPT % 8 == 0, "a lane's channels fill mask bytes");
+  constexpr int NB = (VPT + 7) / 8;
+  const float invn =
+      1.f / (bn.count_ptr ? *bn.count_ptr : (float)bn.count);
+  const int c0 = lane * VPT;
+  const unsigned char* mrow = bn.mask + (long)row * (h >> 3) + (c0 >> 3);
+  unsigned bits[NB];
+#pragma unroll
+  for (int b = 0; b < NB; ++b) bits[b] = mrow[b];
+  float xr[VPT], mu[VPT], is[VPT], ga[VPT], p0[VPT], p1[VPT];
+  S::load(&((const __bf16*)bn.x)[(long)row * h], lane, h, xr);
+  S::load(bn.mean, lane, h, mu);
+  S::load(bn.invstd, lane, h, is);
+  S::load(bn.gamma, lane, h, ga);
+  S::load(bn.partials, lane, h, p0);
+  S::load(bn.partials + h, lane, h, p1);
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) {
+    const bool keep = (bits[j >> 3] >> ((c0 & 7) + (j & 7))) & 1u;
+    gr[j] = (float)bn_bwd_dx16(gr[j], xr[j], keep, mu[j], is[j], ga[j], p0[j],
+                               p1[j], invn, bn.keep_inv);
+  }
+}
+
 template <int VPT, bool VEC, typename QT = float,
           int LPR = PERTGNN_WAVE, typename TG = float, typename PT = float,
           int LPH = LPR, bool PCH = false>
@@ -436,7 +475,7 @@ __global__ void edge_attn_fused_bwd_row_kernel(
     const long* __restrict__ ea, int astride, const float* __restrict__ alpha,
     const int* __restrict__ row_ptr, const int* __restrict__ csr_src,
     QT* __restrict__ dqkvs, float* __restrict__ dal, int n, int h,
-    float scale) {
+    float scale, AttnBnBwd bn = AttnBnBwd{}) {
   // SINGLE pass over the row's edges (the old two-pass form re-gathered
   // ec+ke per edge after sdot was known).  Softmax backward re-expressed:
   //   dq = scale * (Sum a*da*(k+e)  -  sdot * Sum a*(k+e))
@@ -461,6 +500,12 @@ __global__ void edge_attn_fused_bwd_row_kernel(
 
   float gr[VPT], a1[VPT], a2[VPT];
   S::load(&g[(long)row * h], lane, h, gr);
+  // g is the BN OUTPUT gradient when bn.x is set (wave-uniform): the row's
+  // gradient is then formed here, and stored as dskip below like any other
+  // (h = 256 / 512 only: VPT <= 16 in every lane mapping of those widths)
+  if constexpr (VEC && std::is_same<TG, __bf16>::value && VPT <= 16) {
+    if (bn.x) attn_bn_bwd_row<VPT>(bn, row, lane, h, gr);
+  }
 #pragma unroll
   for (int j = 0; j < VPT; ++j) { a1[j] = 0.f; a2[j] = 0.f; }
 
@@ -554,11 +599,16 @@ template <int VPT, bool VEC, typename QT = float, typename ET = float,
           int LPR = PERTGNN_WAVE, typename TG = float, int LPH = LPR,
           bool PCH = false>
 __global__ void edge_attn_fused_bwd_col_kernel(
-    const TG* __restrict__ g, const QT* __restrict__ qkvs,
+    const TG* g, const QT* __restrict__ qkvs,
     const float* __restrict__ alpha, const float* __restrict__ dal,
     const int* __restrict__ col_ptr, const int* __restrict__ csc_dst,
-    const int* __restrict__ csc_eid, QT* __restrict__ dqkvs,
-    ET* __restrict__ de, int n, int h) {
+    const int* __restrict__ csc_eid, QT* dqkvs,
+    ET* __restrict__ de, int n, int h, long gld) {
+  // g rows lie gld elements apart: h for a compact [n, h] gradient, 4h when
+  // g is the dskip segment of dqkvs that the row kernel wrote before this
+  // kernel started (same stream).  g and dqkvs then share an allocation —
+  // the columns read (3h..4h) and written (h..3h) are disjoint — so neither
+  // pointer is __restrict__.
   using S = Slice<VPT, VEC>;
   static_assert(VEC || LPR == PERTGNN_WAVE, "sub-wave rows need VEC layout");
   static_assert(PCH ? !VEC : (VEC || LPH == LPR),
@@ -585,7 +635,7 @@ __global__ void edge_attn_fused_bwd_col_kernel(
       const long dst = csc_dst[p];
       float qd[VPT], gd[VPT], des[VPT];
       S::load(&qkvs[dst * ld], lane, h, qd);
-      S::load(&g[dst * h], lane, h, gd);
+      S::load(&g[dst * gld], lane, h, gd);
 #pragma unroll
       for (int j = 0; j < VPT; ++j) {
         const bool live = lane + j * PERTGNN_WAVE < h;
@@ -611,7 +661,7 @@ __global__ void edge_attn_fused_bwd_col_kernel(
     const float a = alpha[eid * HM::HEADS + hd];
     float qd[VPT], gd[VPT], des[VPT];
     S::load(&qkvs[dst * ld], lane, h, qd);
-    S::load(&g[dst * h], lane, h, gd);
+    S::load(&g[dst * gld], lane, h, gd);
 #pragma unroll
     for (int j = 0; j < VPT; ++j) {
       const float dk1 = dl * qd[j];
@@ -774,7 +824,7 @@ void launch_edge_attn_fused_bwd(const float* g, const float* qkvs,
                                        n, h, scale);                           \
       edge_attn_fused_bwd_col_kernel<V, true, float, float, LPR, float, LPH>   \
           <<<grid, block, 0, stream>>>(g, qkvs, alpha, dal, col_ptr, csc_dst,  \
-                                       csc_eid, dqkvs, de, n, h);              \
+                                       csc_eid, dqkvs, de, n, h, h);           \
     }                                                                          \
   } while (0)
 #define BWD_PCH(V, LPR, C)                                                     \
@@ -788,7 +838,7 @@ void launch_edge_attn_fused_bwd(const float* g, const float* qkvs,
       edge_attn_fused_bwd_col_kernel<V, false, float, float, LPR, float, C,    \
                                      true>                                     \
           <<<grid, block, 0, stream>>>(g, qkvs, alpha, dal, col_ptr, csc_dst,  \
-                                       csc_eid, dqkvs, de, n, h);              \
+                                       csc_eid, dqkvs, de, n, h, h);           \
     }                                                                          \
   } while (0)
     const char* name = "edge_attn_fused launcher";
@@ -822,13 +872,13 @@ void launch_edge_attn_fused_bwd(const float* g, const float* qkvs,
           g, qkvs, pifc, prpc, ea, astride, alpha, row_ptr, csr_src, dqkvs,    \
           dal, n, h, scale);                                                   \
       edge_attn_fused_bwd_col_kernel<V, true><<<grid, block, 0, stream>>>(     \
-          g, qkvs, alpha, dal, col_ptr, csc_dst, csc_eid, dqkvs, de, n, h);    \
+          g, qkvs, alpha, dal, col_ptr, csc_dst, csc_eid, dqkvs, de, n, h, h); \
     } else {                                                                   \
       edge_attn_fused_bwd_row_kernel<V, false><<<grid, block, 0, stream>>>(    \
           g, qkvs, pifc, prpc, ea, astride, alpha, row_ptr, csr_src, dqkvs,    \
           dal, n, h, scale);                                                   \
       edge_attn_fused_bwd_col_kernel<V, false><<<grid, block, 0, stream>>>(    \
-          g, qkvs, alpha, dal, col_ptr, csc_dst, csc_eid, dqkvs, de, n, h);    \
+          g, qkvs, alpha, dal, col_ptr, csc_dst, csc_eid, dqkvs, de, n, h, h); \
     }                                                                          \
     break;
     CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
@@ -934,10 +984,19 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
                                   const int* csc_dst, const int* csc_eid,
                                   void* dqkvs_v, void* de_v, float* dal,
                                   int n, int h, long num_edges, int heads,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, const AttnBnBwd* bn) {
   const __bf16* qkvs = (const __bf16*)qkvs_v;
   __bf16* dqkvs = (__bf16*)dqkvs_v;
   __bf16* de = (__bf16*)de_v;
+  // bn (may be null): g_v is the gradient of the BN OUTPUT; the row kernel
+  // applies the BN backward to each row it loads and the col kernel gathers
+  // the result from the dskip columns the row kernel wrote (bf16 g only)
+  if (bn && (!g16 || (h != 256 && h != 512)))
+    pertgnn_shape_fail("edge_attn_fused act16 launcher",
+                       g16 ? "bn, h" : "bn with fp32 g, h", h);
+  const AttnBnBwd bnk = bn ? *bn : AttnBnBwd{};
+  const __bf16* gcol = bn ? dqkvs + 3L * h : (const __bf16*)g_v;
+  const long gld = bn ? 4L * h : h;
   if (n == 0 && heads == 1) return;
   const float scale =
       attn_heads_ok(h, heads) ? 1.f / std::sqrt((float)(h / heads)) : 0.f;
@@ -956,12 +1015,12 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
                                        (const __bf16*)pifc_v,                  \
                                        (const __bf16*)prpc_v,                  \
                                        ea, astride, alpha, row_ptr, csr_src,   \
-                                       dqkvs, dal, n, h, scale);               \
+                                       dqkvs, dal, n, h, scale, bnk);          \
       edge_attn_fused_bwd_col_kernel<VPT, true, __bf16, __bf16, LPR, __bf16,   \
                                      LPH>                                      \
-          <<<grid, block, 0, stream>>>((const __bf16*)g_v, qkvs, alpha, dal,   \
-                                       col_ptr, csc_dst, csc_eid, dqkvs, de,   \
-                                       n, h);                                  \
+          <<<grid, block, 0, stream>>>(gcol, qkvs, alpha, dal, col_ptr,        \
+                                       csc_dst, csc_eid, dqkvs, de, n, h,      \
+                                       gld);                                   \
     } else if (g16) {                                                          \
       edge_attn_fused_bwd_row_kernel<VPT, true, __bf16, LPR, __bf16, float,    \
                                      LPH>                                      \
@@ -969,12 +1028,12 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
                                        (const float*)pifc_v,                   \
                                        (const float*)prpc_v,                   \
                                        ea, astride, alpha, row_ptr, csr_src,   \
-                                       dqkvs, dal, n, h, scale);               \
+                                       dqkvs, dal, n, h, scale, bnk);          \
       edge_attn_fused_bwd_col_kernel<VPT, true, __bf16, __bf16, LPR, __bf16,   \
                                      LPH>                                      \
-          <<<grid, block, 0, stream>>>((const __bf16*)g_v, qkvs, alpha, dal,   \
-                                       col_ptr, csc_dst, csc_eid, dqkvs, de,   \
-                                       n, h);                                  \
+          <<<grid, block, 0, stream>>>(gcol, qkvs, alpha, dal, col_ptr,        \
+                                       csc_dst, csc_eid, dqkvs, de, n, h,      \
+                                       gld);                                   \
     } else if (p16) {                                                          \
       /* fp32 upstream grad (the last conv's out16=false) + bf16 P tables — \
          reading the tables at the wrong width over-reads 2x (OOB) */        \
@@ -989,7 +1048,7 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
                                      LPH>                                      \
           <<<grid, block, 0, stream>>>((const float*)g_v, qkvs, alpha, dal,    \
                                        col_ptr, csc_dst, csc_eid, dqkvs, de,   \
-                                       n, h);                                  \
+                                       n, h, h);                               \
     } else {                                                                   \
       edge_attn_fused_bwd_row_kernel<VPT, true, __bf16, LPR, float, float,     \
                                      LPH>                                      \
@@ -1002,7 +1061,7 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
                                      LPH>                                      \
           <<<grid, block, 0, stream>>>((const float*)g_v, qkvs, alpha, dal,    \
                                        col_ptr, csc_dst, csc_eid, dqkvs, de,   \
-                                       n, h);                                  \
+                                       n, h, h);                               \
     }                                                                          \
   } while (0)
 #define BWD16_H(VPT, LPR)                                                      \

@@ -1903,13 +1903,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_wide_kernel(
     }
     __bf16 ov[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      float gm = gv[u] * keep_inv;
-      if (!((bits >> u) & 1u)) gm = 0.f;
-      const float xhat = (xv[u] - mu[u]) * is[u];
-      ov[u] = (__bf16)(ga[u] * is[u] *
-                       (gm - p0[u] * invn - xhat * p1[u] * invn));
-    }
+    for (int u = 0; u < 8; ++u)
+      ov[u] = bn_bwd_dx16(gv[u], xv[u], (bits >> u) & 1u, mu[u], is[u], ga[u],
+                          p0[u], p1[u], invn, keep_inv);
     bn_st8(&dx[t], ov);
   }
 }
@@ -2190,6 +2186,24 @@ void launch_bn_bwd_partials_only16(const void* g, const void* x,
   bn_bwd_partials_dispatch((const __bf16*)g, (const __bf16*)x,
                            (const __bf16*)y, mean, invstd, n, h, relu,
                            partials, keep_inv, s);
+}
+
+// first half of launch_bn_bwd16 on the keep-mask path (training forward with
+// ReLU on a fast-path shape): partials[2h] plus dgamma/dbeta, no dx — the
+// attention backward applies the element-wise part itself
+void launch_bn_bwd_partials_affine16(const void* g, const void* x,
+                                     const unsigned char* mask,
+                                     const float* mean, const float* invstd,
+                                     long n, int h, float* partials,
+                                     float keep_inv, float* slab,
+                                     float* dgamma, float* dbeta,
+                                     hipStream_t s) {
+  if (n <= 0 || !mask || !bn_wide_ok(h))
+    pertgnn_shape_fail("bn_bwd_partials_affine16", "h", h);
+  bn_bwd_partials_wide_launch((const __bf16*)g, (const __bf16*)x,
+                              (const __bf16*)nullptr, mask, mean, invstd, n,
+                              h, true, partials, slab, dgamma, dbeta,
+                              keep_inv, s);
 }
 
 void launch_bn_bwd_apply_only16(const void* g, const void* x, const void* y,

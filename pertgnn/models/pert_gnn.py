@@ -219,6 +219,26 @@ class TransformerConv(nn.Module):
         through the attention kernels.  ``pifc`` / ``prpc``: this layer's
         bf16 P tables when the caller computed all layers' at once
         (``ops.ptables_grouped``); without them they are computed here."""
+        qkvs, pifc, prpc = self._fused_operands(x, ifc_weight, rpc_weight,
+                                                pifc, prpc)
+        return ops.edge_attention_fused(qkvs, pifc, prpc, edge_attr, csr,
+                                        out16=out16, heads=self.heads)
+
+    def forward_fused_bn(self, x, edge_attr, ifc_weight, rpc_weight, csr, bn,
+                         comm=None, dropout_p=0.0, pifc=None, prpc=None):
+        """``forward_fused(..., out16=True)`` followed by the training
+        BN+ReLU(+dropout) of ``bn`` as one autograd node, whose attention
+        backward applies the BN backward (act16 mode only; the caller checks
+        ``ops.bn_attn_fuse_enabled``)."""
+        qkvs, pifc, prpc = self._fused_operands(x, ifc_weight, rpc_weight,
+                                                pifc, prpc)
+        return ops.edge_attention_fused_bn_relu(
+            qkvs, pifc, prpc, edge_attr, csr, bn.weight, bn.bias,
+            bn.running_mean, bn.running_var, bn.momentum, bn.eps,
+            heads=self.heads, comm=comm, dropout_p=dropout_p)
+
+    def _fused_operands(self, x, ifc_weight, rpc_weight, pifc, prpc):
+        """qkvs and the two P tables of the fused attention op."""
         h = self.out_channels
         # w4/b4 ARE the parameters (no per-step cat); the storage is
         # pre-padded to k_padded with zero columns (zero-grad columns stay
@@ -245,8 +265,7 @@ class TransformerConv(nn.Module):
             qkvs = ops.linear(x, self.w4, self.b4)
             pifc = ops.linear(ifc_weight, self.we_ifc, None)
             prpc = ops.linear(rpc_weight, self.we_rpc, None)
-        return ops.edge_attention_fused(qkvs, pifc, prpc, edge_attr, csr,
-                                        out16=out16, heads=self.heads)
+        return qkvs, pifc, prpc
 
 
 class SAGEDeterministic(nn.Module):
@@ -381,16 +400,30 @@ class SAGEDeterministic(nn.Module):
         # act16: BN (and the embed concat above) emit bf16 activations so
         # every conv's fused QKVS GEMM and its backward read/write 16-bit
         # streams; gate matches the linear16 gate in forward_fused.
+        # training in act16 mode: conv + BN are one autograd node, so that the
+        # attention backward applies the BN backward (the BN keep mask exists
+        # for n > 0 at the widths bn_attn_fuse_enabled names)
+        fuse_bn = (out16 and self.training and n > 0
+                   and ops.bn_attn_fuse_enabled(hidden))
         for i, conv in enumerate(self.convs[:-1]):
-            x = run_conv(conv, x, out16=out16)
             bn = self.bns[i]
-            # dropout fused into the BN epilogue (K8); the CPU oracle path
-            # applies torch dropout inside batchnorm_relu
-            x = ops.batchnorm_relu(
-                x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                bn.momentum, bn.eps, self.training, fuse_relu=True,
-                comm=self._bn_comm, out16=out16, dropout_p=self.dropout,
-            )
+            if fuse_bn:
+                pifc, prpc = ptables.get(id(conv), (None, None))
+                x = conv.forward_fused_bn(
+                    x, edge_attr, self.interface_embeds.weight,
+                    self.rpctype_embeds.weight, csr, bn,
+                    comm=self._bn_comm, dropout_p=self.dropout,
+                    pifc=pifc, prpc=prpc,
+                )
+            else:
+                x = run_conv(conv, x, out16=out16)
+                # dropout fused into the BN epilogue (K8); the CPU oracle
+                # path applies torch dropout inside batchnorm_relu
+                x = ops.batchnorm_relu(
+                    x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                    bn.momentum, bn.eps, self.training, fuse_relu=True,
+                    comm=self._bn_comm, out16=out16, dropout_p=self.dropout,
+                )
             if self.training and bn.track_running_stats and bn.num_batches_tracked is not None:
                 bn.num_batches_tracked += 1
         x = run_conv(self.convs[-1], x)

@@ -528,32 +528,38 @@ class _EdgeAttentionFusedFn(torch.autograd.Function):
             g.contiguous(), qkvs, pifc, prpc, edge_attr, alpha,
             row_ptr, csr_src, col_ptr, csc_dst, csc_eid, ctx.heads,
         )
-        # dP tables (per-vocab segment sums of de) are independent of the
-        # CSC dk/dv pass queued above — overlap them on the side stream.
-        if not _overlap_enabled():
-            h = de.shape[1]
-            if (h % 256 == 0 and not deterministic()
-                    and (pifc.shape[0] + prpc.shape[0]) * h * 4 <= 160 * 1024):
-                dpifc, dprpc = m.vocab_scatter_dual(de, edge_attr, pifc.shape[0], prpc.shape[0])
-                if dpifc.dtype != pifc.dtype:  # bf16 P tables: match grad dtype
-                    dpifc = dpifc.to(pifc.dtype)
-                    dprpc = dprpc.to(prpc.dtype)
-            else:
-                dpifc, dprpc = _edge_table_grads(m, de, pifc, prpc, edge_attr)
-            return dqkvs, dpifc, dprpc, None, None, None, None, None, None, None, None
-        cur = torch.cuda.current_stream()
-        side = _side_stream()
-        ev = torch.cuda.Event()
-        ev.record(cur)
-        side.wait_event(ev)
-        with torch.cuda.stream(side):
-            dpifc, dprpc = _edge_table_grads(m, de, pifc, prpc, edge_attr)
-        ev2 = torch.cuda.Event()
-        ev2.record(side)
-        cur.wait_event(ev2)
-        _mark_cross_stream(dpifc, cur)
-        _mark_cross_stream(dprpc, cur)
+        dpifc, dprpc = _attn_table_grads(m, de, pifc, prpc, edge_attr)
         return dqkvs, dpifc, dprpc, None, None, None, None, None, None, None, None
+
+
+def _attn_table_grads(m, de, pifc, prpc, edge_attr):
+    """dP_ifc, dP_rpc of a fused attention backward from its de."""
+    # dP tables (per-vocab segment sums of de) are independent of the
+    # CSC dk/dv pass queued above — overlap them on the side stream.
+    if not _overlap_enabled():
+        h = de.shape[1]
+        if (h % 256 == 0 and not deterministic()
+                and (pifc.shape[0] + prpc.shape[0]) * h * 4 <= 160 * 1024):
+            dpifc, dprpc = m.vocab_scatter_dual(de, edge_attr, pifc.shape[0], prpc.shape[0])
+            if dpifc.dtype != pifc.dtype:  # bf16 P tables: match grad dtype
+                dpifc = dpifc.to(pifc.dtype)
+                dprpc = dprpc.to(prpc.dtype)
+        else:
+            dpifc, dprpc = _edge_table_grads(m, de, pifc, prpc, edge_attr)
+        return dpifc, dprpc
+    cur = torch.cuda.current_stream()
+    side = _side_stream()
+    ev = torch.cuda.Event()
+    ev.record(cur)
+    side.wait_event(ev)
+    with torch.cuda.stream(side):
+        dpifc, dprpc = _edge_table_grads(m, de, pifc, prpc, edge_attr)
+    ev2 = torch.cuda.Event()
+    ev2.record(side)
+    cur.wait_event(ev2)
+    _mark_cross_stream(dpifc, cur)
+    _mark_cross_stream(dprpc, cur)
+    return dpifc, dprpc
 
 
 def _fused_eager(qkvs, pifc, prpc, edge_attr, csr, heads):
@@ -766,50 +772,60 @@ def _rng_counter(device):
     return t
 
 
+def _bn_forward(m, x, gamma, beta, running_mean, running_var, momentum, eps,
+                training, fuse_relu, comm, dropout_p):
+    """BN(+ReLU+dropout) forward ops, local or sync.  Returns (y, save_mean,
+    save_invstd, mask or None, sync, keep_inv)."""
+    sync = comm is not None and getattr(comm, "distributed", False) and training
+    drop = float(dropout_p) if training else 0.0
+    if drop > 0.0:
+        assert fuse_relu, "fused dropout rides the ReLU mask (model.py:102-103)"
+    seed = _rng_counter(x.device) if drop > 0.0 else torch.empty(
+        0, dtype=torch.int64, device=x.device)
+    if sync:
+        # sync-BN (SURVEY.md §7 hard part 4, exact-parity mode): ONE
+        # all-reduce carries the partial sums AND the row count (tail
+        # slot of the [2h+1] partials) — no host round-trip per layer,
+        # so the whole step stays launch-async (and hipGraph-capturable
+        # where the backend supports captured collectives).
+        partials = m.bn_stats(x)
+        comm.all_reduce_(partials)
+        fin = (m.bn_finalize_apply16 if x.dtype == torch.bfloat16
+               else m.bn_finalize_apply)
+        out = fin(
+            x, partials, gamma, beta, running_mean, running_var,
+            momentum, eps, training, fuse_relu, drop, seed)
+    else:
+        fwd = (m.bn_relu_fwd16 if x.dtype == torch.bfloat16
+               else m.bn_relu_fwd)
+        out = fwd(
+            x, gamma, beta, running_mean, running_var, momentum, eps,
+            training, fuse_relu, drop, seed
+        )
+    y, save_mean, save_invstd = out[:3]
+    # the bf16 training forward with ReLU also returns a bit-packed keep
+    # mask [n, h/8] (uint8); the backward reads that instead of y, and
+    # the next layer's linear still holds y for its own wgrad
+    mask = out[3] if len(out) > 3 and out[3].numel() > 0 else None
+    # post-dropout y==0 <=> dropped-or-relu-negative, so the backward
+    # only needs the keep scale on the existing y<=0 mask (no RNG)
+    keep_inv = 1.0 / (1.0 - drop) if drop > 0.0 else 1.0
+    return y, save_mean, save_invstd, mask, sync, keep_inv
+
+
 class _BNReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps,
                 training, fuse_relu, comm, out16=False, dropout_p=0.0):
-        m = ext()
-        sync = comm is not None and getattr(comm, "distributed", False) and training
-        drop = float(dropout_p) if training else 0.0
-        if drop > 0.0:
-            assert fuse_relu, "fused dropout rides the ReLU mask (model.py:102-103)"
-        seed = _rng_counter(x.device) if drop > 0.0 else torch.empty(
-            0, dtype=torch.int64, device=x.device)
-        if sync:
-            # sync-BN (SURVEY.md §7 hard part 4, exact-parity mode): ONE
-            # all-reduce carries the partial sums AND the row count (tail
-            # slot of the [2h+1] partials) — no host round-trip per layer,
-            # so the whole step stays launch-async (and hipGraph-capturable
-            # where the backend supports captured collectives).
-            partials = m.bn_stats(x)
-            comm.all_reduce_(partials)
-            fin = (m.bn_finalize_apply16 if x.dtype == torch.bfloat16
-                   else m.bn_finalize_apply)
-            out = fin(
-                x, partials, gamma, beta, running_mean, running_var,
-                momentum, eps, training, fuse_relu, drop, seed)
-        else:
-            fwd = (m.bn_relu_fwd16 if x.dtype == torch.bfloat16
-                   else m.bn_relu_fwd)
-            out = fwd(
-                x, gamma, beta, running_mean, running_var, momentum, eps,
-                training, fuse_relu, drop, seed
-            )
-        y, save_mean, save_invstd = out[:3]
-        # the bf16 training forward with ReLU also returns a bit-packed keep
-        # mask [n, h/8] (uint8); the backward reads that instead of y, and
-        # the next layer's linear still holds y for its own wgrad
-        mask = out[3] if len(out) > 3 and out[3].numel() > 0 else None
+        y, save_mean, save_invstd, mask, sync, keep_inv = _bn_forward(
+            ext(), x, gamma, beta, running_mean, running_var, momentum, eps,
+            training, fuse_relu, comm, dropout_p)
         ctx.save_for_backward(x, gamma, save_mean, save_invstd,
                               y if mask is None else mask)
         ctx.y16 = y.dtype == torch.bfloat16
         ctx.fuse_relu = fuse_relu
         ctx.comm = comm if sync else None
-        # post-dropout y==0 <=> dropped-or-relu-negative, so the backward
-        # only needs the keep scale on the existing y<=0 mask (no RNG)
-        ctx.keep_inv = 1.0 / (1.0 - drop) if drop > 0.0 else 1.0
+        ctx.keep_inv = keep_inv
         return y
 
     @staticmethod
@@ -838,6 +854,82 @@ class _BNReLUFn(torch.autograd.Function):
             )
         return (dx, dgamma, dbeta, None, None, None, None, None, None, None,
                 None, None)
+
+
+def bn_attn_fuse_enabled(h: int) -> bool:
+    """The attention backward applies the BN backward of the BN that follows
+    it (act16 training, h in {256, 512}: the widths both the keep mask and
+    the bf16 attention kernels cover).  PERTGNN_NO_BN_ATTN_FUSE=1 keeps the
+    two separate Functions; read per call so one process can run both."""
+    import os
+    return (h in (256, 512)
+            and os.environ.get("PERTGNN_NO_BN_ATTN_FUSE", "0") != "1")
+
+
+class _AttnBNReLUFn(torch.autograd.Function):
+    """Fused attention forward -> BN+ReLU(+dropout) training forward, act16.
+    The forward is the two existing ops; the backward hands the BN output
+    gradient to the attention backward, whose row kernel applies the BN
+    backward to each row it loads — the [N, H] dx between the two is never
+    written."""
+
+    @staticmethod
+    def forward(ctx, qkvs, pifc, prpc, gamma, beta, edge_attr, row_ptr,
+                csr_src, col_ptr, csc_dst, csc_eid, heads, running_mean,
+                running_var, momentum, eps, comm, dropout_p):
+        m = ext()
+        x, alpha = m.edge_attn_fused_fwd(qkvs, pifc, prpc, edge_attr, row_ptr,
+                                         csr_src, True, heads)
+        y, save_mean, save_invstd, mask, sync, keep_inv = _bn_forward(
+            m, x, gamma, beta, running_mean, running_var, momentum, eps,
+            True, True, comm, dropout_p)
+        if mask is None:
+            raise RuntimeError(
+                "fused attention+BN needs the BN keep mask (n > 0, H in "
+                f"{{256, 512}}); got x {tuple(x.shape)}")
+        ctx.save_for_backward(qkvs, pifc, prpc, gamma, edge_attr, alpha,
+                              row_ptr, csr_src, col_ptr, csc_dst, csc_eid,
+                              x, save_mean, save_invstd, mask)
+        ctx.heads = heads
+        ctx.comm = comm if sync else None
+        ctx.keep_inv = keep_inv
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (qkvs, pifc, prpc, gamma, edge_attr, alpha, row_ptr, csr_src, col_ptr,
+         csc_dst, csc_eid, x, save_mean, save_invstd, mask) = ctx.saved_tensors
+        m = ext()
+        g = g.contiguous()
+        partials = ()
+        if ctx.comm is not None:
+            # as _BNReLUFn.backward: local [2h+1] partials, one all-reduce
+            # for the global sums and count
+            partials_local = m.bn_bwd_partials16(
+                g, x, mask, save_mean, save_invstd, True, ctx.keep_inv)
+            partials_global = partials_local.clone()
+            ctx.comm.all_reduce_(partials_global)
+            partials = (partials_global, partials_local)
+        dqkvs, de, dgamma, dbeta = m.edge_attn_bn_bwd16(
+            g, x, mask, gamma, save_mean, save_invstd, ctx.keep_inv, qkvs,
+            pifc, prpc, edge_attr, alpha, row_ptr, csr_src, col_ptr, csc_dst,
+            csc_eid, ctx.heads, *partials)
+        dpifc, dprpc = _attn_table_grads(m, de, pifc, prpc, edge_attr)
+        return (dqkvs, dpifc, dprpc, dgamma, dbeta) + (None,) * 13
+
+
+def edge_attention_fused_bn_relu(qkvs, pifc, prpc, edge_attr, csr, gamma,
+                                 beta, running_mean, running_var, momentum,
+                                 eps, heads=1, comm=None, dropout_p=0.0):
+    """``batchnorm_relu(edge_attention_fused(..., out16=True), training=True,
+    fuse_relu=True, out16=True)`` as one autograd node (bf16 ``qkvs`` on the
+    GPU, ``bn_attn_fuse_enabled(h)``): same forward ops, same results, one
+    pass over [N, H] less in the backward."""
+    row_ptr, csr_src, col_ptr, csc_dst, csc_eid = csr
+    return _AttnBNReLUFn.apply(
+        qkvs, pifc, prpc, gamma, beta, edge_attr, row_ptr, csr_src, col_ptr,
+        csc_dst, csc_eid, heads, running_mean, running_var, momentum, eps,
+        comm, dropout_p)
 
 
 class _EagerSyncBNFn(torch.autograd.Function):
@@ -1072,6 +1164,8 @@ __all__ = [
     "edge_attention",
     "edge_attention_fused",
     "edge_attention_fused_infer",
+    "edge_attention_fused_bn_relu",
+    "bn_attn_fuse_enabled",
     "embedding",
     "pattern_pool",
     "embed_concat_node",
