@@ -193,10 +193,11 @@ void launch_vocab_scatter_dual16(const void*, const long*, int, float*,
                                  float*, long, int, int, int, hipStream_t);
 void launch_gemm_bf16_nt_o16(const float*, const float*, const float*, void*,
                              int, int, int, hipStream_t);
-void launch_gemm_a16_glds_nt(const void*, const void*, const float*,
-                             const float*, void*, int, int, int, int, bool,
-                             hipStream_t);
+void launch_gemm_a16_glds_nt(const void*, const void*, const float*, void*,
+                             int, int, int, int, bool, hipStream_t);
 void launch_convert_w16(const float*, void*, long, hipStream_t);
+void launch_convert_w16_both(const float*, void*, void*, int, int,
+                             hipStream_t);
 void launch_gemm_a16_glds_tn(const void*, const void*, float*, float*, int,
                              int, int, hipStream_t);
 void launch_transpose_convert_w16(const float*, void*, int, int, hipStream_t);
@@ -1440,39 +1441,87 @@ torch::Tensor seg_pool_bwd16(torch::Tensor gout, torch::Tensor probs,
   return dx;
 }
 
-torch::Tensor linear_fwd_a16o16(torch::Tensor x, torch::Tensor w,
-                                torch::Tensor b, bool fp16c = false) {
+// Gate of the dgrad-as-glds-NT path (linear_dgrad16_o16), shared with the
+// forward so that it can hand over the transposed weight image.
+static bool dgrad_glds_ok(int m, int n, int k) {
+  return m >= 512 && k % 128 == 0 && n % 64 == 0;
+}
+
+// -> (y, wt16): y = x . w^T + b in bf16.  With want_wt, and where the dgrad
+// gate will accept the shape, wt16 is the transposed bf16 weight image
+// [k, n] that the dgrad consumes, written by the same launch that makes the
+// forward's own [n, k] image; otherwise it is an empty tensor.
+static std::vector<torch::Tensor> linear_fwd_a16o16_impl(torch::Tensor x,
+                                                         torch::Tensor w,
+                                                         torch::Tensor b,
+                                                         bool fp16c,
+                                                         bool want_wt) {
   CHECK_IN(x); CHECK_IN(w);
   const int m = x.size(0);
   const int k = x.size(1);
   const int n = w.size(0);
   auto y = torch::empty({m, n}, x.options());  // bf16
+  auto wt16 = torch::empty({0}, x.options());
   const float* bias = nullptr;
   if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
   if (fp16c) {
     launch_gemm_fp16_nt_a16o16(x.data_ptr(), w.data_ptr<float>(), bias,
                                y.data_ptr(), m, n, k, cur_stream());
-    return y;
+    return {y, wt16};
   }
   // glds fast path (direct-to-LDS staging): needs 16-B-aligned rows, full
   // BK tiles in k, and n a multiple of the 128-wide tile.  The bf16 weight
   // copy costs one trivial convert kernel per call (n*k elements).
   if (m >= 512 && n % 128 == 0 && k % 32 == 0) {
     auto w16 = torch::empty({n, k}, x.options());  // bf16
-    launch_convert_w16(w.data_ptr<float>(), w16.data_ptr(), (long)n * k,
-                       cur_stream());
-    launch_gemm_a16_glds_nt(x.data_ptr(), w16.data_ptr(),
-                            w.data_ptr<float>(), bias, y.data_ptr(),
+    if (want_wt && dgrad_glds_ok(m, n, k)) {
+      wt16 = torch::empty({k, n}, x.options());  // bf16, transposed
+      launch_convert_w16_both(w.data_ptr<float>(), w16.data_ptr(),
+                              wt16.data_ptr(), n, k, cur_stream());
+    } else {
+      launch_convert_w16(w.data_ptr<float>(), w16.data_ptr(), (long)n * k,
+                         cur_stream());
+    }
+    launch_gemm_a16_glds_nt(x.data_ptr(), w16.data_ptr(), bias, y.data_ptr(),
                             /*c16=*/1, m, n, k, false, cur_stream());
-    return y;
+    return {y, wt16};
   }
   launch_gemm_bf16_nt_a16o16(x.data_ptr(), w.data_ptr<float>(), bias,
                              y.data_ptr(), m, n, k, cur_stream());
-  return y;
+  return {y, wt16};
+}
+
+// -> (w16 [n, k], wt16 [k, n]): the two bf16 weight images on their own
+std::vector<torch::Tensor> convert_w16_both(torch::Tensor w) {
+  CHECK_IN(w);
+  TORCH_CHECK(w.scalar_type() == torch::kFloat32 && w.dim() == 2,
+              "w must be fp32 [n, k]");
+  const int n = w.size(0);
+  const int k = w.size(1);
+  auto opt = w.options().dtype(torch::kBFloat16);
+  auto w16 = torch::empty({n, k}, opt);
+  auto wt16 = torch::empty({k, n}, opt);
+  launch_convert_w16_both(w.data_ptr<float>(), w16.data_ptr(),
+                          wt16.data_ptr(), n, k, cur_stream());
+  return {w16, wt16};
+}
+
+torch::Tensor linear_fwd_a16o16(torch::Tensor x, torch::Tensor w,
+                                torch::Tensor b, bool fp16c = false) {
+  return linear_fwd_a16o16_impl(x, w, b, fp16c, false)[0];
+}
+
+std::vector<torch::Tensor> linear_fwd_a16o16_wt(torch::Tensor x,
+                                                torch::Tensor w,
+                                                torch::Tensor b,
+                                                bool fp16c = false) {
+  return linear_fwd_a16o16_impl(x, w, b, fp16c, true);
 }
 
 torch::Tensor linear_dgrad16_o16(torch::Tensor g, torch::Tensor w,
-                                 bool fp16c = false) {
+                                 bool fp16c = false,
+                                 c10::optional<torch::Tensor> wt16_in =
+                                     c10::nullopt) {
   CHECK_IN(g); CHECK_IN(w);
   const int m = g.size(0);
   const int n = w.size(0);
@@ -1483,24 +1532,26 @@ torch::Tensor linear_dgrad16_o16(torch::Tensor g, torch::Tensor w,
                                dx.data_ptr(), m, n, k, cur_stream());
     return dx;
   }
-  // dgrad as glds-NT: dx[M,k] = g[M,n] . (w^T)[k,n]^T — one transposed
-  // bf16 copy of the weight turns the NN contraction into the NT fast
-  // path; the m-tail strip runs the register-staging NN kernel on the
-  // original fp32 weight.
-  if (m >= 512 && k % 128 == 0 && n % 64 == 0) {
-    auto wt16 = torch::empty({k, n}, g.options());  // bf16, transposed
-    launch_transpose_convert_w16(w.data_ptr<float>(), wt16.data_ptr(), n, k,
-                                 cur_stream());
-    launch_gemm_a16_glds_nt(g.data_ptr(), wt16.data_ptr(), nullptr, nullptr,
+  // dgrad as glds-NT: dx[M,k] = g[M,n] . (w^T)[k,n]^T — a transposed bf16
+  // copy of the weight turns the NN contraction into the NT fast path.  The
+  // forward hands the copy over (wt16_in) where it made one; otherwise it
+  // is converted here.
+  if (dgrad_glds_ok(m, n, k)) {
+    torch::Tensor wt16;
+    if (wt16_in.has_value() && wt16_in->defined() && wt16_in->numel() > 0) {
+      wt16 = *wt16_in;
+      CHECK_IN(wt16);
+      TORCH_CHECK(wt16.scalar_type() == torch::kBFloat16 && wt16.dim() == 2 &&
+                      wt16.size(0) == k && wt16.size(1) == n,
+                  "wt16 must be the bf16 [k, n] image of w");
+    } else {
+      wt16 = torch::empty({k, n}, g.options());  // bf16, transposed
+      launch_transpose_convert_w16(w.data_ptr<float>(), wt16.data_ptr(), n, k,
+                                   cur_stream());
+    }
+    launch_gemm_a16_glds_nt(g.data_ptr(), wt16.data_ptr(), nullptr,
                             dx.data_ptr(), /*c16=*/1, m, k, n, false,
                             cur_stream());
-    const int m_done = m - m % 128;
-    if (m_done < m)
-      launch_gemm_bf16_nn_a16o16(
-          (const char*)g.data_ptr() + (long)m_done * n * 2,
-          w.data_ptr<float>(),
-          (char*)dx.data_ptr() + (long)m_done * k * 2, m - m_done, n, k,
-          cur_stream());
     return dx;
   }
   launch_gemm_bf16_nn_a16o16(g.data_ptr(), w.data_ptr<float>(),
@@ -1516,11 +1567,15 @@ std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
   const int k = x.size(1);
   const int n = g.size(1);
   auto fopt = x.options().dtype(torch::kFloat32);
-  auto dw = torch::empty({n, k}, fopt);
+  // dw and db are views of one buffer, so the glds path clears both with a
+  // single memset (the other paths clear the two views on their own)
+  const long nk = (long)n * k;
+  auto buf = torch::empty({nk + (has_bias ? n : 0)}, fopt);
+  auto dw = buf.narrow(0, 0, nk).view({n, k});
   torch::Tensor db = torch::empty({0}, fopt);
   float* db_ptr = nullptr;
   if (has_bias) {
-    db = torch::empty({n}, fopt);
+    db = buf.narrow(0, nk, n);
     db_ptr = db.data_ptr<float>();
   }
   if (fp16c) {
@@ -1802,8 +1857,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("seg_pool_bwd16", &seg_pool_bwd16);
   mod.def("linear_fwd_a16o16", &linear_fwd_a16o16, py::arg("x"), py::arg("w"),
           py::arg("b"), py::arg("fp16c") = false);
+  mod.def("convert_w16_both", &convert_w16_both, py::arg("w"));
+  mod.def("linear_fwd_a16o16_wt", &linear_fwd_a16o16_wt, py::arg("x"),
+          py::arg("w"), py::arg("b"), py::arg("fp16c") = false);
   mod.def("linear_dgrad16_o16", &linear_dgrad16_o16, py::arg("g"),
-          py::arg("w"), py::arg("fp16c") = false);
+          py::arg("w"), py::arg("fp16c") = false,
+          py::arg("wt16") = py::none());
   mod.def("linear_wgrad16_b16", &linear_wgrad16_b16, py::arg("g"),
           py::arg("x"), py::arg("has_bias"), py::arg("fp16c") = false);
   mod.def("bn_relu_fwd", &bn_relu_fwd, py::arg("x"), py::arg("gamma"),

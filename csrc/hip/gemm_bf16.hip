@@ -892,9 +892,10 @@ void launch_gemm_fp16_tn_a16b16(const void* a_v, const void* b_v, float* c,
 // 8-row group one 32-B slot over (guide: bank-conflict 141x down).
 // One barrier per K-step: issue next tile's glds -> MFMA current ->
 // s_waitcnt vmcnt(0) -> barrier (the accepted step-3 stall).
-// Interior tiles only — the launcher routes edge tiles (m tail) to the
-// register-staging kernel via pointer offset; requires k % BK == 0 and
-// 16-B-aligned rows (lda % 8 == 0).
+// The grid covers ceil(m / BM) row tiles: the partial last tile stages
+// clamped (duplicate) A rows and skips the stores of rows >= m, so its valid
+// rows get exactly the arithmetic of interior rows.  Requires n % BN == 0,
+// k % BK == 0 and 16-B-aligned rows (lda % 8 == 0).
 // ---------------------------------------------------------------------------
 
 __device__ __forceinline__ unsigned glds_swz(unsigned byte_off) {
@@ -941,15 +942,30 @@ __global__ void gemm_a16_glds_nt_kernel(const __bf16* __restrict__ a,
   const int src_kb = (int)(l_off % ROW_BYTES);     // byte within row
 
   const long lda = k;  // elements
-  // per-operand group counts: A covers BM rows, B covers BN (they differ
-  // for the single-column-tile dgrad variant)
-  auto stage = [&]<int GRPS>(const __bf16* g, int g0, int k0, __bf16* lds) {
+  // per-lane source bases (byte offsets at k0 = 0), fixed before the K loop.
+  // The A rows of the edge tile (m0 + BM > m) are clamped to m - 1: the
+  // block stages duplicates of a valid row, never reads past the tensor,
+  // and the epilogue drops the rows >= m.  B always has full tiles.
+  // Per-operand group counts: A covers BM rows, B covers BN (they differ
+  // for the single-column-tile dgrad variant).
+  long a_base[GRPS_A / NWAVE], b_base[GRPS_B / NWAVE];
+#pragma unroll
+  for (int i = 0; i < GRPS_A / NWAVE; ++i) {
+    const int row = m0 + (wave + i * NWAVE) * ROWS_PER_GRP + src_row;
+    a_base[i] = (long)min(row, m - 1) * lda * 2 + src_kb;
+  }
+#pragma unroll
+  for (int i = 0; i < GRPS_B / NWAVE; ++i) {
+    const int row = n0 + (wave + i * NWAVE) * ROWS_PER_GRP + src_row;
+    b_base[i] = (long)row * lda * 2 + src_kb;
+  }
+  auto stage = [&]<int GRPS>(const __bf16* g, const long* base, int k0,
+                             __bf16* lds) {
 #pragma unroll
     for (int i = 0; i < GRPS / NWAVE; ++i) {
       const int grp = wave + i * NWAVE;
-      const __bf16* src = (const __bf16*)((const char*)g +
-          (long)(g0 + grp * ROWS_PER_GRP + src_row) * lda * 2 +
-          (long)k0 * 2 + src_kb);
+      const __bf16* src =
+          (const __bf16*)((const char*)g + base[i] + (long)k0 * 2);
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)src,
           (__attribute__((address_space(3))) void*)(lds + grp * 512),
@@ -963,8 +979,8 @@ __global__ void gemm_a16_glds_nt_kernel(const __bf16* __restrict__ a,
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
 
-  stage.template operator()<GRPS_A>(a, m0, 0, lds_ab(0));
-  stage.template operator()<GRPS_B>(b, n0, 0, lds_bb(0));
+  stage.template operator()<GRPS_A>(a, a_base, 0, lds_ab(0));
+  stage.template operator()<GRPS_B>(b, b_base, 0, lds_bb(0));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -998,8 +1014,8 @@ __global__ void gemm_a16_glds_nt_kernel(const __bf16* __restrict__ a,
 
   int buf = 0;
   for (int k0 = BK; k0 < k; k0 += BK) {
-    stage.template operator()<GRPS_A>(a, m0, k0, lds_ab(buf ^ 1));
-    stage.template operator()<GRPS_B>(b, n0, k0, lds_bb(buf ^ 1));
+    stage.template operator()<GRPS_A>(a, a_base, k0, lds_ab(buf ^ 1));
+    stage.template operator()<GRPS_B>(b, b_base, k0, lds_bb(buf ^ 1));
     mma(lds_ab(buf), lds_bb(buf));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1041,8 +1057,10 @@ __global__ void gemm_a16_glds_nt_kernel(const __bf16* __restrict__ a,
       const int r = chunk / CPR;
       const int off = (chunk % CPR) * EPL;
       const u32x4_t val = *reinterpret_cast<const u32x4_t*>(&scratch[r * SW + off]);
-      u32x4_t* dst = reinterpret_cast<u32x4_t*>(
-          &c[(long)(m0 + wm + mi * 16 + r) * n + n0 + wn + off]);
+      const int grow = m0 + wm + mi * 16 + r;
+      if (grow >= m) continue;  // edge tile: rows past the tensor
+      u32x4_t* dst =
+          reinterpret_cast<u32x4_t*>(&c[(long)grow * n + n0 + wn + off]);
       if constexpr (NTC)
         __builtin_nontemporal_store(val, dst);
       else
@@ -1080,6 +1098,43 @@ __global__ void transpose_convert_w16_kernel(const float* __restrict__ w,
   }
 }
 
+// Both bf16 weight images of one fp32 [rows][cols] weight from one launch:
+// o [rows][cols] for the forward, ot [cols][rows] for the dgrad-as-NT.  Each
+// 32x32 tile is read once; the same (__bf16) rounding as the two kernels
+// above, so the images are bit-identical to theirs.
+__global__ void convert_w16_both_kernel(const float* __restrict__ w,
+                                        __bf16* __restrict__ o,
+                                        __bf16* __restrict__ ot, int rows,
+                                        int cols) {
+  __shared__ float tile[32][33];
+  const int c0 = blockIdx.x * 32;
+  const int r0 = blockIdx.y * 32;
+  const int tx = threadIdx.x % 32;
+  const int ty = threadIdx.x / 32;
+  for (int dy = ty; dy < 32; dy += blockDim.x / 32) {
+    const int r = r0 + dy, ccol = c0 + tx;
+    float v = 0.f;
+    if (r < rows && ccol < cols) {
+      v = w[(long)r * cols + ccol];
+      o[(long)r * cols + ccol] = (__bf16)v;
+    }
+    tile[dy][tx] = v;
+  }
+  __syncthreads();
+  for (int dy = ty; dy < 32; dy += blockDim.x / 32) {
+    const int ccol = c0 + dy, r = r0 + tx;
+    if (ccol < cols && r < rows)
+      ot[(long)ccol * rows + r] = (__bf16)tile[tx][dy];
+  }
+}
+
+void launch_convert_w16_both(const float* w, void* o, void* ot, int rows,
+                             int cols, hipStream_t s) {
+  convert_w16_both_kernel<<<dim3((cols + 31) / 32, (rows + 31) / 32),
+                            dim3(256), 0, s>>>(w, (__bf16*)o, (__bf16*)ot,
+                                               rows, cols);
+}
+
 void launch_convert_w16(const float* w, void* o, long numel, hipStream_t s) {
   const int blocks = (int)min((numel + 255) / 256, (long)4096);
   convert_w16_kernel<<<blocks, 256, 0, s>>>(w, (__bf16*)o, numel);
@@ -1091,10 +1146,8 @@ void launch_transpose_convert_w16(const float* w, void* o, int rows, int cols,
                                  dim3(256), 0, s>>>(w, (__bf16*)o, rows, cols);
 }
 
-// A + B16 bf16, NT: full interior tiles through the glds kernel, the
-// m-tail strip through the register-staging kernel (pointer offset; it
-// stages the ORIGINAL fp32 weights, rounding to the same bf16 values the
-// convert kernel produced).
+// A + B16 bf16, NT: every row tile, the partial last one included, runs in
+// the one glds launch.
 static int glds_bk() {  // default 32 (measured: +13-20% over 64 at model shapes)
   static int v = [] {
     const char* e = getenv("PERTGNN_GLDS_BK");
@@ -1127,17 +1180,17 @@ static bool glds_n256() {  // 256-wide output tile for big dgrads (default ON)
 }
 
 void launch_gemm_a16_glds_nt(const void* a_v, const void* b16_v,
-                             const float* b32, const float* bias, void* c_v,
-                             int c16, int m, int n, int k, bool relu,
-                             hipStream_t s) {
+                             const float* bias, void* c_v, int c16, int m,
+                             int n, int k, bool relu, hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
   const __bf16* b = (const __bf16*)b16_v;
   constexpr int BM = 128, BN = 128;
-  const int mt = m / BM;  // full row tiles
-  if (mt >= 1024 && n == 256 && k % 32 == 0 && glds_n256()) {
+  if (m <= 0) return;
+  const int mt = (m + BM - 1) / BM;  // row tiles, the partial last one included
+  if (m / BM >= 1024 && n == 256 && k % 32 == 0 && glds_n256()) {
     // single-column-tile variant for the dgrad shape: A is streamed exactly
     // once and the per-block K-loop halves its barrier count (measured
-    // +12% at [180k,1024]x[1024,256]); needs mt >= ~1024 blocks to fill
+    // +12% at [180k,1024]x[1024,256]); needs >= ~1024 full row tiles to fill
     // the chip (it LOSES at 45k rows where the 128-wide grid is 2x larger)
     if (c16)
       gemm_a16_glds_nt_kernel<128, 256, 32, __bf16, 512, true>
@@ -1147,7 +1200,7 @@ void launch_gemm_a16_glds_nt(const void* a_v, const void* b16_v,
       gemm_a16_glds_nt_kernel<128, 256, 32, float, 512, true>
           <<<dim3(mt), dim3(512), 0, s>>>(a, b, bias, (float*)c_v, m, n, k,
                                           relu ? 1 : 0);
-  } else if (mt > 0) {
+  } else {
     const int grid = mt * (n / BN);
     const int bk = glds_bk();
     const bool t512 = glds_t512();
@@ -1171,21 +1224,6 @@ void launch_gemm_a16_glds_nt(const void* a_v, const void* b16_v,
       else      { if (ntc) GLDS_DISPATCH(64, 256, true); else GLDS_DISPATCH(64, 256, false); }
     }
 #undef GLDS_DISPATCH
-  }
-  const int m_done = mt * BM;
-  if (m_done < m && b32) {  // tail strip via the register-staging kernel
-    const int ms = m - m_done;
-    const int grid = ((ms + 63) / 64) * ((n + 63) / 64);
-    if (c16)
-      gemm_bf16_nt_kernel<64, 64, 64, __bf16, __bf16, __bf16>
-          <<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(
-              a + (long)m_done * k, b32, bias,
-              (__bf16*)c_v + (long)m_done * n, ms, n, k, relu ? 1 : 0);
-    else
-      gemm_bf16_nt_kernel<64, 64, 64, __bf16, __bf16, float>
-          <<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(
-              a + (long)m_done * k, b32, bias,
-              (float*)c_v + (long)m_done * n, ms, n, k, relu ? 1 : 0);
   }
 }
 
@@ -1235,8 +1273,8 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
   const int wm = (wave / WCOL) * (BM / 2);
   const int wn = (wave % WCOL) * (BN / WCOL);
 
-  // m range of this slice (multiples of BKM; the launcher routes the
-  // global m tail to the register-staging kernel)
+  // m range of this slice (multiples of BKM; the m % BKM rows behind
+  // m_full are a partial last step of the last slice, below)
   const int m_full = m - m % BKM;
   const int per_slice = ((m_full / BKM + slices - 1) / slices) * BKM;
   const int c_beg = slice * per_slice;
@@ -1245,17 +1283,19 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
 
   // panel-major glds staging: group g covers half a panel (32 m x 16 cols);
   // lane's 16-B chunk = 8 columns of one m-row of the panel
-  auto stage = [&](const __bf16* src_base, long ld, int col0, int mrow0,
-                   char* lds) {
+  // (TAIL: the partial last step clamps the m-row to m - 1, so it stages
+  // duplicates of a valid row and never reads past the tensor)
+  auto stage = [&]<bool TAIL = false>(const __bf16* src_base, long ld,
+                                      int col0, int mrow0, char* lds) {
 #pragma unroll
     for (int i = 0; i < GRPS_PER_WAVE; ++i) {
       const int grp = wave + i * NWAVE;
       const int panel = grp / (PANEL_BYTES / 1024);
       const int half = grp % (PANEL_BYTES / 1024);
-      const int mrow = half * ROWS_PER_GRP + (lane >> 1);
+      int mrow = mrow0 + half * ROWS_PER_GRP + (lane >> 1);
+      if constexpr (TAIL) mrow = min(mrow, m - 1);
       const int col = panel * 16 + (lane & 1) * 8;
-      const __bf16* src =
-          src_base + (long)(mrow0 + mrow) * ld + col0 + col;
+      const __bf16* src = src_base + (long)mrow * ld + col0 + col;
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)src,
           (__attribute__((address_space(3))) void*)(lds + grp * 1024),
@@ -1335,7 +1375,34 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
     __syncthreads();
     buf ^= 1;
   }
+  // m tail: the slice that ends at m_full owns the m % BKM rows behind it
+  // as one more, partial, step.  Every wave left the other buffer at the
+  // loop's last barrier, so it is staged under the final full step's MFMAs;
+  // block-uniform and run once, hence not part of the double-buffered loop.
+  const int rem = m - m_full;
+  const bool tail = rem > 0 && c_end == m_full;
+  if (tail) {
+    stage.template operator()<true>(a, n, n0, m_full, lds_ab(buf ^ 1));
+    stage.template operator()<true>(b, k2, k0, m_full, lds_bb(buf ^ 1));
+  }
   mma(lds_ab(buf), lds_bb(buf));
+  if (tail) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // zero the rows >= rem of every [BKM][16] panel in BOTH images (32 B
+    // per row and panel): a zero on one side only would turn an Inf in the
+    // duplicated row of the other into a NaN
+    const u32x4_t z = {0u, 0u, 0u, 0u};
+    for (int t = threadIdx.x; t < (BM + BN) / 16 * BKM * 2; t += THREADS) {
+      const bool in_b = t >= BM / 16 * BKM * 2;
+      const int u = in_b ? t - BM / 16 * BKM * 2 : t;  // 16-B chunk in image
+      if ((u >> 1) % BKM >= rem)
+        *reinterpret_cast<u32x4_t*>(
+            (in_b ? lds_bb(buf ^ 1) : lds_ab(buf ^ 1)) + u * 16) = z;
+    }
+    __syncthreads();
+    mma(lds_ab(buf ^ 1), lds_bb(buf ^ 1));
+  }
   if (do_bias && wave % WCOL == 0) {
 #pragma unroll
     for (int mi = 0; mi < FM; ++mi) {
@@ -1364,42 +1431,10 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
       }
 }
 
-// m-tail of the TN wgrad: C[n,k2] += sum_{i<mt} g[i,n_idx]*x[i,k_idx] for the
-// mt (< BKM) rows past the last full m tile.  The work is tiny (mt*n*k2
-// MACs) but the register-staging kernel used to run it on a
-// (n/128)*(k2/128)-block grid — 16-32 workgroups of guarded scalar staging,
-// ~107 us for 0.01 GFLOP at [26,1024,256].  Here one block owns one output
-// ROW of C (grid = n, fills the chip), threads stride k2: the x reads are
-// lane-coalesced, g[i,jn] is a wave-broadcast scalar, and the contribution
-// is atomicAdd-combined with the main kernel's slices exactly like an extra
-// split-K slice.
-__global__ void gemm_tail_tn_kernel(const __bf16* __restrict__ g,
-                                    const __bf16* __restrict__ b,
-                                    float* __restrict__ c,
-                                    float* __restrict__ dbias, int mt, int n,
-                                    int k2) {
-  const int jn = blockIdx.x;
-  if (dbias && threadIdx.x == 0) {
-    float s = 0.f;
-    for (int i = 0; i < mt; ++i) s += (float)g[(long)i * n + jn];
-    atomicAdd(&dbias[jn], s);
-  }
-  for (int jk = threadIdx.x; jk < k2; jk += blockDim.x) {
-    float a0 = 0.f, a1 = 0.f;
-    int i = 0;
-    for (; i + 2 <= mt; i += 2) {
-      a0 += (float)g[(long)i * n + jn] * (float)b[(long)i * k2 + jk];
-      a1 += (float)g[(long)(i + 1) * n + jn] * (float)b[(long)(i + 1) * k2 + jk];
-    }
-    if (i < mt)
-      a0 += (float)g[(long)i * n + jn] * (float)b[(long)i * k2 + jk];
-    atomicAdd(&c[(long)jn * k2 + jk], a0 + a1);
-  }
-}
-
-// Both operands bf16 contract-major (g [m][n], x [m][k2]); m tail rows
-// beyond the last BKM multiple run gemm_tail_tn_kernel as an extra atomic
-// slice.
+// Both operands bf16 contract-major (g [m][n], x [m][k2]); the m tail rows
+// beyond the last BKM multiple are a partial last step inside the kernel.
+// When dbias sits right behind c (one [n*k2 + n] buffer, as the binding
+// allocates them) a single memset clears both.
 void launch_gemm_a16_glds_tn(const void* a_v, const void* b_v, float* c,
                              float* dbias, int m, int n, int k2,
                              hipStream_t s) {
@@ -1407,21 +1442,22 @@ void launch_gemm_a16_glds_tn(const void* a_v, const void* b_v, float* c,
   const __bf16* b = (const __bf16*)b_v;
   constexpr int BM = 128, BN = 128, BKM = 64;
   const int tiles = (n / BM) * (k2 / BN);
+  // split-K over the full BKM steps; the tail step rides the last slice and
+  // does not change the split (m and m - m % BKM slice alike)
   int slices = 1;
   while (tiles * slices < 512 && slices < 64 &&
-         (long)slices * BKM * 4 < m)
+         (long)slices * BKM * 4 < m - m % BKM)
     slices *= 2;
-  HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
-  if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
+  const long nc = (long)n * k2;
+  if (dbias == c + nc) {
+    HIP_CHECK(hipMemsetAsync(c, 0, (nc + n) * sizeof(float), s));
+  } else {
+    HIP_CHECK(hipMemsetAsync(c, 0, nc * sizeof(float), s));
+    if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
+  }
   gemm_a16_glds_tn_kernel<BM, BN, BKM>
       <<<dim3(tiles * slices), dim3(512), 0, s>>>(a, b, c, dbias, m, n, k2,
                                                   slices);
-  const int m_full = m - m % BKM;
-  if (m_full < m) {
-    gemm_tail_tn_kernel<<<dim3(n), dim3(256), 0, s>>>(
-        a + (long)m_full * n, b + (long)m_full * k2, c, dbias, m - m_full, n,
-        k2);
-  }
 }
 
 // ---------------------------------------------------------------------------

@@ -399,8 +399,16 @@ class _Linear16Fn(torch.autograd.Function):
         m = ext()
         bb = b if b is not None else torch.empty(0, dtype=torch.float32, device=x.device)
         fp16c = gemm_precision() == "fp16"  # fp16 matrix cores, bf16 IO
+        # the forward's weight-convert launch also writes the transposed bf16
+        # image the dgrad needs (w cannot change in between: it stays a saved
+        # tensor, so autograd's version check catches an in-place update)
+        ctx.wt16 = None
         if x.dtype == torch.bfloat16:
-            y = m.linear_fwd_a16o16(x, w, bb, fp16c)   # x16 in, bf16 out
+            if any(ctx.needs_input_grad):
+                y, wt16 = m.linear_fwd_a16o16_wt(x, w, bb, fp16c)
+                ctx.wt16 = wt16 if wt16.numel() else None
+            else:
+                y = m.linear_fwd_a16o16(x, w, bb, fp16c)   # x16 in, bf16 out
         else:
             y = m.linear_fwd_bf16_o16(x, w, bb)
         ctx.save_for_backward(x, w)
@@ -414,7 +422,7 @@ class _Linear16Fn(torch.autograd.Function):
         m = ext()
         g = g.contiguous()
         if x.dtype == torch.bfloat16:
-            dx = m.linear_dgrad16_o16(g, w, ctx.fp16c)
+            dx = m.linear_dgrad16_o16(g, w, ctx.fp16c, ctx.wt16)
             dw, db = m.linear_wgrad16_b16(g, x, ctx.has_bias, ctx.fp16c)
         else:
             dx = m.linear_dgrad16(g, w)
