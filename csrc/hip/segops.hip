@@ -1027,6 +1027,7 @@ void launch_embed_node_fwd(const float* x_raw, const long* idx,
 void launch_embed_node_fwd16(const float* x_raw, const long* idx,
                              const float* table, void* out, long n, int f,
                              int h, hipStream_t stream) {
+  if (n == 0) return;
   const long numel = n * (long)(f + h);
   const int tpb = 256;
   const int blocks = (int)min((numel + tpb - 1) / tpb, (long)4096);
@@ -2337,6 +2338,11 @@ __global__ void eval_metrics_kernel(const float* __restrict__ y,
 
 void launch_quantile_loss_fwd(const float* y, const float* y_hat, float* out,
                               long b, float tau, hipStream_t s) {
+  if (b == 0) {
+    // mean over no elements: NaN (all-ones is a quiet NaN), nothing launched
+    HIP_CHECK(hipMemsetAsync(out, 0xFF, sizeof(float), s));
+    return;
+  }
   HIP_CHECK(hipMemsetAsync(out, 0, sizeof(float), s));
   quantile_loss_fwd_kernel<<<grid_for(b, 256, 256), 256, 0, s>>>(y, y_hat, out,
                                                                  b, tau);
@@ -2344,12 +2350,14 @@ void launch_quantile_loss_fwd(const float* y, const float* y_hat, float* out,
 void launch_quantile_loss_bwd(const float* g, const float* y,
                               const float* y_hat, float* dy_hat, long b,
                               float tau, hipStream_t s) {
+  if (b == 0) return;
   quantile_loss_bwd_kernel<<<grid_for(b), 256, 0, s>>>(g, y, y_hat, dy_hat, b,
                                                        tau);
 }
 void launch_eval_metrics(const float* y, const float* y_hat, float* out3,
                          long b, float tau, hipStream_t s) {
   HIP_CHECK(hipMemsetAsync(out3, 0, 3 * sizeof(float), s));
+  if (b == 0) return;  // empty sums: three zeros
   eval_metrics_kernel<<<grid_for(b, 256, 256), 256, 0, s>>>(y, y_hat, out3, b,
                                                             tau);
 }

@@ -92,7 +92,8 @@ def _group_by(idx: torch.Tensor, rows: int, iters_target: int | None = None):
     entry is live)."""
     if iters_target is None:
         iters_target = _scatter_iters()
-    key = (idx.data_ptr(), idx.numel(), tuple(idx.stride()), rows)
+    key = (idx.data_ptr(), idx.numel(), tuple(idx.stride()), rows,
+           iters_target)
     hit = _GROUP_CACHE.get(key)
     if hit is not None:
         _GROUP_CACHE.move_to_end(key)
