@@ -2,12 +2,16 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
+#include <climits>
 #include <cstdlib>
 #include <optional>
+#include <string>
+#include <vector>
 
 #include <c10/cuda/CUDAStream.h>
 
 #include "hip/attn_bn.h"
+#include "hip/gemm_dispatch.h"
 
 namespace {
 
@@ -510,6 +514,7 @@ torch::Tensor linear_fwd_bf16(torch::Tensor x, torch::Tensor w,
   const int k = x.size(1);
   const int n = w.size(0);
   auto y = torch::empty({m, n}, x.options());
+  if (m == 0) return y;  // no rows: nothing to launch
   const float* bias = nullptr;
   if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
   launch_gemm_bf16_nt(x.data_ptr<float>(), w.data_ptr<float>(), bias,
@@ -524,6 +529,9 @@ std::vector<torch::Tensor> linear_bwd_bf16(torch::Tensor g, torch::Tensor x,
   const int k = x.size(1);
   const int n = w.size(0);
   auto dx = torch::empty({m, k}, x.options());
+  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
+    return {dx, torch::zeros({n, k}, w.options()),
+            torch::zeros({has_bias ? n : 0}, g.options())};
   auto dw = torch::empty({n, k}, w.options());
   torch::Tensor db = torch::empty({0}, g.options());
   float* db_ptr = nullptr;
@@ -541,6 +549,7 @@ std::vector<torch::Tensor> linear_bwd_bf16(torch::Tensor g, torch::Tensor x,
 torch::Tensor gemm_nt_bf16(torch::Tensor a, torch::Tensor b) {
   CHECK_IN(a); CHECK_IN(b);
   auto c = torch::empty({a.size(0), b.size(0)}, a.options());
+  if (a.size(0) == 0) return c;  // no rows: nothing to launch
   launch_gemm_bf16_nt(a.data_ptr<float>(), b.data_ptr<float>(), nullptr,
                       c.data_ptr<float>(), a.size(0), b.size(0), a.size(1),
                       false, cur_stream());
@@ -549,6 +558,7 @@ torch::Tensor gemm_nt_bf16(torch::Tensor a, torch::Tensor b) {
 torch::Tensor gemm_nn_bf16(torch::Tensor a, torch::Tensor b) {
   CHECK_IN(a); CHECK_IN(b);
   auto c = torch::empty({a.size(0), b.size(1)}, a.options());
+  if (a.size(0) == 0) return c;  // no rows: nothing to launch
   launch_gemm_bf16_nn(a.data_ptr<float>(), b.data_ptr<float>(), nullptr,
                       c.data_ptr<float>(), a.size(0), a.size(1), b.size(1),
                       false, cur_stream());
@@ -556,6 +566,8 @@ torch::Tensor gemm_nn_bf16(torch::Tensor a, torch::Tensor b) {
 }
 torch::Tensor gemm_tn_bf16(torch::Tensor a, torch::Tensor b) {
   CHECK_IN(a); CHECK_IN(b);
+  if (a.size(0) == 0)  // empty contraction: zeros, nothing to launch
+    return torch::zeros({a.size(1), b.size(1)}, a.options());
   auto c = torch::empty({a.size(1), b.size(1)}, a.options());
   launch_gemm_bf16_tn(a.data_ptr<float>(), b.data_ptr<float>(),
                       c.data_ptr<float>(), nullptr, a.size(0), a.size(1),
@@ -570,6 +582,7 @@ torch::Tensor linear_fwd_fp16(torch::Tensor x, torch::Tensor w,
   const int k = x.size(1);
   const int n = w.size(0);
   auto y = torch::empty({m, n}, x.options());
+  if (m == 0) return y;  // no rows: nothing to launch
   const float* bias = nullptr;
   if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
   launch_gemm_fp16_nt(x.data_ptr<float>(), w.data_ptr<float>(), bias,
@@ -584,6 +597,9 @@ std::vector<torch::Tensor> linear_bwd_fp16(torch::Tensor g, torch::Tensor x,
   const int k = x.size(1);
   const int n = w.size(0);
   auto dx = torch::empty({m, k}, x.options());
+  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
+    return {dx, torch::zeros({n, k}, w.options()),
+            torch::zeros({has_bias ? n : 0}, g.options())};
   auto dw = torch::empty({n, k}, w.options());
   torch::Tensor db = torch::empty({0}, g.options());
   float* db_ptr = nullptr;
@@ -605,6 +621,7 @@ torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b) {
   const int n = w.size(0);
   TORCH_CHECK(w.size(1) == k, "weight shape mismatch");
   auto y = torch::empty({m, n}, x.options());
+  if (m == 0) return y;  // no rows: nothing to launch
   const float* bias = nullptr;
   if (b.defined() && b.numel() > 0) {
     CHECK_IN(b);
@@ -622,6 +639,9 @@ std::vector<torch::Tensor> linear_bwd(torch::Tensor g, torch::Tensor x,
   const int k = x.size(1);
   const int n = w.size(0);
   auto dx = torch::empty({m, k}, x.options());
+  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
+    return {dx, torch::zeros({n, k}, w.options()),
+            torch::zeros({has_bias ? n : 0}, g.options())};
   auto dw = torch::empty({n, k}, w.options());
   torch::Tensor db = torch::empty({0}, g.options());
   float* db_ptr = nullptr;
@@ -640,6 +660,7 @@ std::vector<torch::Tensor> linear_bwd(torch::Tensor g, torch::Tensor x,
 torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor b) {
   CHECK_IN(a); CHECK_IN(b);
   auto c = torch::empty({a.size(0), b.size(0)}, a.options());
+  if (a.size(0) == 0) return c;  // no rows: nothing to launch
   launch_gemm_f32_nt(a.data_ptr<float>(), b.data_ptr<float>(), nullptr,
                      c.data_ptr<float>(), a.size(0), b.size(0), a.size(1),
                      false, cur_stream());
@@ -648,6 +669,7 @@ torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor b) {
 torch::Tensor gemm_nn(torch::Tensor a, torch::Tensor b) {
   CHECK_IN(a); CHECK_IN(b);
   auto c = torch::empty({a.size(0), b.size(1)}, a.options());
+  if (a.size(0) == 0) return c;  // no rows: nothing to launch
   launch_gemm_f32_nn(a.data_ptr<float>(), b.data_ptr<float>(), nullptr,
                      c.data_ptr<float>(), a.size(0), a.size(1), b.size(1),
                      false, cur_stream());
@@ -655,6 +677,8 @@ torch::Tensor gemm_nn(torch::Tensor a, torch::Tensor b) {
 }
 torch::Tensor gemm_tn(torch::Tensor a, torch::Tensor b) {
   CHECK_IN(a); CHECK_IN(b);
+  if (a.size(0) == 0)  // empty contraction: zeros, nothing to launch
+    return torch::zeros({a.size(1), b.size(1)}, a.options());
   auto c = torch::empty({a.size(1), b.size(1)}, a.options());
   launch_gemm_f32_tn(a.data_ptr<float>(), b.data_ptr<float>(),
                      c.data_ptr<float>(), nullptr, a.size(0), a.size(1),
@@ -1059,6 +1083,7 @@ torch::Tensor linear_dgrad(torch::Tensor g, torch::Tensor w, int64_t prec) {
   const int n = w.size(0);
   const int k = w.size(1);
   auto dx = torch::empty({m, k}, g.options());
+  if (m == 0) return dx;  // no rows: nothing to launch
   if (prec == 1)
     launch_gemm_bf16_nn(g.data_ptr<float>(), w.data_ptr<float>(), nullptr,
                         dx.data_ptr<float>(), m, n, k, false, cur_stream());
@@ -1077,6 +1102,9 @@ std::vector<torch::Tensor> linear_wgrad(torch::Tensor g, torch::Tensor x,
   const int m = x.size(0);
   const int k = x.size(1);
   const int n = g.size(1);
+  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
+    return {torch::zeros({n, k}, x.options()),
+            torch::zeros({has_bias ? n : 0}, g.options())};
   auto dw = torch::empty({n, k}, x.options());
   torch::Tensor db = torch::empty({0}, g.options());
   float* db_ptr = nullptr;
@@ -1128,6 +1156,7 @@ torch::Tensor linear_fwd_bf16_o16(torch::Tensor x, torch::Tensor w,
   const int k = x.size(1);
   const int n = w.size(0);
   auto y = torch::empty({m, n}, x.options().dtype(torch::kBFloat16));
+  if (m == 0) return y;  // no rows: nothing to launch
   const float* bias = nullptr;
   if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
   launch_gemm_bf16_nt_o16(x.data_ptr<float>(), w.data_ptr<float>(), bias,
@@ -1142,7 +1171,8 @@ torch::Tensor linear_dgrad16(torch::Tensor g, torch::Tensor w) {
   const int n = w.size(0);
   const int k = w.size(1);
   auto dx = torch::empty({m, k}, w.options());
-  if (m <= 16) {  // tiny-row P-table backward: see gemm_skinny_nn_kernel
+  if (m == 0) return dx;  // no rows: nothing to launch
+  if (gemm_dispatch::dgrad_skinny(m)) {  // tiny-row P-table backward
     launch_gemm_skinny_nn(g.data_ptr(), w.data_ptr<float>(),
                           dx.data_ptr<float>(), m, n, k, cur_stream());
     return dx;
@@ -1159,6 +1189,9 @@ std::vector<torch::Tensor> linear_wgrad16(torch::Tensor g, torch::Tensor x,
   const int m = x.size(0);
   const int k = x.size(1);
   const int n = g.size(1);
+  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
+    return {torch::zeros({n, k}, x.options()),
+            torch::zeros({has_bias ? n : 0}, x.options())};
   auto dw = torch::empty({n, k}, x.options());
   torch::Tensor db = torch::empty({0}, x.options());
   float* db_ptr = nullptr;
@@ -1443,9 +1476,7 @@ torch::Tensor seg_pool_bwd16(torch::Tensor gout, torch::Tensor probs,
 
 // Gate of the dgrad-as-glds-NT path (linear_dgrad16_o16), shared with the
 // forward so that it can hand over the transposed weight image.
-static bool dgrad_glds_ok(int m, int n, int k) {
-  return m >= 512 && k % 128 == 0 && n % 64 == 0;
-}
+using gemm_dispatch::dgrad_glds_ok;
 
 // -> (y, wt16): y = x . w^T + b in bf16.  With want_wt, and where the dgrad
 // gate will accept the shape, wt16 is the transposed bf16 weight image
@@ -1462,6 +1493,7 @@ static std::vector<torch::Tensor> linear_fwd_a16o16_impl(torch::Tensor x,
   const int n = w.size(0);
   auto y = torch::empty({m, n}, x.options());  // bf16
   auto wt16 = torch::empty({0}, x.options());
+  if (m == 0) return {y, wt16};  // no rows: nothing to launch
   const float* bias = nullptr;
   if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
   if (fp16c) {
@@ -1472,7 +1504,7 @@ static std::vector<torch::Tensor> linear_fwd_a16o16_impl(torch::Tensor x,
   // glds fast path (direct-to-LDS staging): needs 16-B-aligned rows, full
   // BK tiles in k, and n a multiple of the 128-wide tile.  The bf16 weight
   // copy costs one trivial convert kernel per call (n*k elements).
-  if (m >= 512 && n % 128 == 0 && k % 32 == 0) {
+  if (gemm_dispatch::fwd_glds_ok(m, n, k)) {
     auto w16 = torch::empty({n, k}, x.options());  // bf16
     if (want_wt && dgrad_glds_ok(m, n, k)) {
       wt16 = torch::empty({k, n}, x.options());  // bf16, transposed
@@ -1527,6 +1559,7 @@ torch::Tensor linear_dgrad16_o16(torch::Tensor g, torch::Tensor w,
   const int n = w.size(0);
   const int k = w.size(1);
   auto dx = torch::empty({m, k}, g.options());  // bf16
+  if (m == 0) return dx;  // no rows: nothing to launch
   if (fp16c) {
     launch_gemm_fp16_nn_a16o16(g.data_ptr(), w.data_ptr<float>(),
                                dx.data_ptr(), m, n, k, cur_stream());
@@ -1567,6 +1600,8 @@ std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
   const int k = x.size(1);
   const int n = g.size(1);
   auto fopt = x.options().dtype(torch::kFloat32);
+  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
+    return {torch::zeros({n, k}, fopt), torch::zeros({has_bias ? n : 0}, fopt)};
   // dw and db are views of one buffer, so the glds path clears both with a
   // single memset (the other paths clear the two views on their own)
   const long nk = (long)n * k;
@@ -1587,7 +1622,7 @@ std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
   // glds TN fast path (panel-major images + ds_read_b64_tr_b16 fragments);
   // split-K atomics => not for the deterministic mode
   const char* det = getenv("PERTGNN_DETERMINISTIC");
-  if (!(det && det[0] == '1') && m >= 512 && n % 128 == 0 && k % 128 == 0) {
+  if (gemm_dispatch::wgrad_glds_ok(m, n, k, det && det[0] == '1')) {
     launch_gemm_a16_glds_tn(g.data_ptr(), x.data_ptr(), dw.data_ptr<float>(),
                             db_ptr, m, n, k, cur_stream());
     return {dw, db};
@@ -1596,6 +1631,94 @@ std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
                              dw.data_ptr<float>(), db_ptr, m, n, k,
                              cur_stream());
   return {dw, db};
+}
+
+// ---------------------------------------------------------------------------
+// linear_path: which kernel a linear op takes, from the same predicates
+// (hip/gemm_dispatch.h) that the bindings and launchers above decide by.
+// Host arithmetic only: launches nothing and never touches the device.
+//   op   "fwd" (y = x.w^T + b), "dgrad" (dx = g.w), "wgrad" (dw = g^T.x, db)
+//   x [m, k], w [n, k]
+//   io   "f32": linear_fwd / linear_dgrad / linear_wgrad (and gemm_*), fp32
+//               in and out, prec 0 / 1 / 2 = fp32 / bf16 / fp16 compute
+//        "o16": linear_fwd_bf16_o16 / linear_dgrad16 / linear_wgrad16 (fp32
+//               x, bf16 y and g), prec 1
+//        "a16": linear_fwd_a16o16 / linear_dgrad16_o16 / linear_wgrad16_b16
+//               (bf16 x, y and g), prec 1, or 2 for fp16 compute
+// Labels: glds_nt_128x128, glds_nt_128x256, glds_tn, skinny_nn, and
+// {f32,reg}_{nt,nn,tn}_{64,128} (fp32 / register-staging MFMA kernels, tile
+// edge), "_fp16" appended for fp16 compute, "/s=<split-K slices>" appended
+// for wgrad; "none" for m == 0.  The experiment knobs (PERTGNN_GEMM_*,
+// PERTGNN_GLDS_*) are taken at their defaults.
+// ---------------------------------------------------------------------------
+std::string linear_path(const std::string& op, int64_t m64, int64_t n64,
+                        int64_t k64, const std::string& io, int64_t prec,
+                        bool deterministic) {
+  namespace gd = gemm_dispatch;
+  TORCH_CHECK(m64 >= 0 && n64 > 0 && k64 > 0 && m64 <= INT_MAX &&
+                  n64 <= INT_MAX && k64 <= INT_MAX,
+              "linear_path: bad shape");
+  const int m = (int)m64, n = (int)n64, k = (int)k64;
+  const int iop = op == "fwd" ? 0 : op == "dgrad" ? 1 : op == "wgrad" ? 2 : -1;
+  TORCH_CHECK(iop >= 0, "linear_path: op must be fwd, dgrad or wgrad");
+  const bool f32io = io == "f32", o16 = io == "o16", a16 = io == "a16";
+  TORCH_CHECK(f32io || o16 || a16, "linear_path: io must be f32, o16 or a16");
+  TORCH_CHECK(f32io ? (prec >= 0 && prec <= 2)
+                    : o16 ? prec == 1 : (prec == 1 || prec == 2),
+              "linear_path: no binding with this io and prec");
+  if (m == 0) return "none";  // the bindings return before launching
+  const std::string fp16 = prec == 2 ? "_fp16" : "";
+  const std::string fam = prec == 0 ? "f32" : "reg";
+  const auto tile = [](bool big) { return big ? "128" : "64"; };
+  if (iop == 0) {
+    if (a16 && prec == 1 && gd::fwd_glds_ok(m, n, k))
+      return gd::glds_nt_wide(m, n, k) ? "glds_nt_128x256" : "glds_nt_128x128";
+    return fam + "_nt_" + tile(gd::tile128(m, n)) + fp16;
+  }
+  if (iop == 1) {
+    if (a16 && prec == 1 && gd::dgrad_glds_ok(m, n, k))
+      return gd::glds_nt_wide(m, k, n) ? "glds_nt_128x256" : "glds_nt_128x128";
+    if (o16 && gd::dgrad_skinny(m)) return "skinny_nn";
+    return fam + "_nn_" + tile(gd::tile128(m, k)) + fp16;
+  }
+  if (a16 && prec == 1 && gd::wgrad_glds_ok(m, n, k, deterministic))
+    return "glds_tn/s=" +
+           std::to_string(gd::glds_tn_slices(m, (n / 128) * (k / 128)));
+  return fam + "_tn_" + tile(gd::tn_tile128(n, k)) + fp16 + "/s=" +
+         std::to_string(gd::tn_slices(m, gd::tn_tiles(n, k),
+                                      prec == 0 ? 32 : 64, deterministic));
+}
+
+// Every label linear_path can return, as "io|prec|op|label"; the wgrad labels
+// stand once with "/s=1" (plain stores) and once with "/s>1" (atomic split-K).
+std::vector<std::string> linear_path_labels() {
+  std::vector<std::string> out;
+  const auto add = [&](const char* io, int prec, const char* op,
+                       const std::string& label) {
+    out.push_back(std::string(io) + "|" + std::to_string(prec) + "|" + op +
+                  "|" + label);
+  };
+  const auto reg = [&](const char* io, int prec) {
+    const std::string fam = prec == 0 ? "f32" : "reg";
+    const std::string fp16 = prec == 2 ? "_fp16" : "";
+    for (const char* t : {"64", "128"}) {
+      add(io, prec, "fwd", fam + "_nt_" + t + fp16);
+      add(io, prec, "dgrad", fam + "_nn_" + t + fp16);
+      for (const char* s : {"/s=1", "/s>1"})
+        add(io, prec, "wgrad", fam + "_tn_" + t + fp16 + s);
+    }
+  };
+  for (int prec = 0; prec <= 2; ++prec) reg("f32", prec);
+  reg("o16", 1);
+  add("o16", 1, "dgrad", "skinny_nn");
+  reg("a16", 1);
+  reg("a16", 2);
+  for (const char* op : {"fwd", "dgrad"})
+    for (const char* l : {"glds_nt_128x128", "glds_nt_128x256"})
+      add("a16", 1, op, l);
+  for (const char* s : {"/s=1", "/s>1"})
+    add("a16", 1, "wgrad", std::string("glds_tn") + s);
+  return out;
 }
 
 // ---------------------------------------------------------------------------
@@ -1865,6 +1988,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("wt16") = py::none());
   mod.def("linear_wgrad16_b16", &linear_wgrad16_b16, py::arg("g"),
           py::arg("x"), py::arg("has_bias"), py::arg("fp16c") = false);
+  mod.def("linear_path", &linear_path, py::arg("op"), py::arg("m"),
+          py::arg("n"), py::arg("k"), py::arg("io"), py::arg("prec"),
+          py::arg("deterministic") = false);
+  mod.def("linear_path_labels", &linear_path_labels);
   mod.def("bn_relu_fwd", &bn_relu_fwd, py::arg("x"), py::arg("gamma"),
           py::arg("beta"), py::arg("running_mean"), py::arg("running_var"),
           py::arg("momentum"), py::arg("eps"), py::arg("training"),

@@ -17,6 +17,7 @@
 // (16 lanes read 16 consecutive floats of one LDS row).
 
 #include "common.h"
+#include "gemm_dispatch.h"
 #include <cstdlib>
 
 // PERTGNN_DETERMINISTIC=1: collapse split-K wgrad to one slice so the dw/db
@@ -361,7 +362,7 @@ __global__ void colsum_par_kernel(const float* __restrict__ g,
 void launch_gemm_f32_nt(const float* a, const float* b, const float* bias,
                         float* c, int m, int n, int k, bool relu,
                         hipStream_t s) {
-  if (m >= 512 && n >= 128) {
+  if (gemm_dispatch::tile128(m, n)) {
     const int grid = ((m + 127) / 128) * ((n + 127) / 128);
     gemm_f32_nt_kernel<128, 128><<<dim3(grid), dim3(GEMM_THREADS), 0, s>>>(
         a, b, bias, c, m, n, k, relu ? 1 : 0);
@@ -375,7 +376,7 @@ void launch_gemm_f32_nt(const float* a, const float* b, const float* bias,
 void launch_gemm_f32_nn(const float* a, const float* b, const float* bias,
                         float* c, int m, int n, int k2, bool relu,
                         hipStream_t s) {
-  if (m >= 512 && k2 >= 128) {
+  if (gemm_dispatch::tile128(m, k2)) {
     const int grid = ((m + 127) / 128) * ((k2 + 127) / 128);
     gemm_f32_nn_kernel<128, 128><<<dim3(grid), dim3(GEMM_THREADS), 0, s>>>(
         a, b, bias, c, m, n, k2, relu ? 1 : 0);
@@ -388,14 +389,10 @@ void launch_gemm_f32_nn(const float* a, const float* b, const float* bias,
 
 void launch_gemm_f32_tn(const float* a, const float* b, float* c, float* dbias,
                         int m, int n, int k2, hipStream_t s) {
-  const bool big = (n >= 128 && k2 >= 128);
-  const int bm = big ? 128 : 64;
-  const int bn = big ? 128 : 64;
-  const int tiles = ((n + bm - 1) / bm) * ((k2 + bn - 1) / bn);
-  int slices = 1;
-  while (!pertgnn_deterministic() && tiles * slices < 512 && slices < 64 &&
-         (long)slices * GEMM_BK * 4 < m)
-    slices *= 2;
+  const bool big = gemm_dispatch::tn_tile128(n, k2);
+  const int tiles = gemm_dispatch::tn_tiles(n, k2);
+  const int slices =
+      gemm_dispatch::tn_slices(m, tiles, GEMM_BK, pertgnn_deterministic());
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));

@@ -10,6 +10,7 @@
 // makes the 16-lane fragment reads conflict-free (guide §6 G4).
 
 #include "common.h"
+#include "gemm_dispatch.h"
 
 // PERTGNN_DETERMINISTIC=1: collapse split-K wgrad to one slice so the dw/db
 // reduction order is fixed (read per call — tests flip it at runtime)
@@ -529,7 +530,7 @@ static bool gemm_n64() {  // narrow-BN experiment: 128x64 tiles, 4 waves/SIMD
 void launch_gemm_bf16_nt(const float* a, const float* b, const float* bias,
                          float* c, int m, int n, int k, bool relu,
                          hipStream_t s) {
-  if (m >= 512 && n >= 128) {
+  if (gemm_dispatch::tile128(m, n)) {
     if (gemm_n64()) {
       const int grid = ((m + 127) / 128) * ((n + 63) / 64);
       gemm_bf16_nt_kernel<128, 64, 32><<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(
@@ -553,7 +554,7 @@ void launch_gemm_bf16_nt(const float* a, const float* b, const float* bias,
 void launch_gemm_bf16_nn(const float* a, const float* b, const float* bias,
                          float* c, int m, int n, int k2, bool relu,
                          hipStream_t s) {
-  if (m >= 512 && k2 >= 128) {
+  if (gemm_dispatch::tile128(m, k2)) {
     if (gemm_n64()) {
       const int grid = ((m + 127) / 128) * ((k2 + 63) / 64);
       gemm_bf16_nn_kernel<128, 64, 32><<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(
@@ -576,14 +577,10 @@ void launch_gemm_bf16_nn(const float* a, const float* b, const float* bias,
 
 void launch_gemm_bf16_tn(const float* a, const float* b, float* c,
                          float* dbias, int m, int n, int k2, hipStream_t s) {
-  const bool big = (n >= 128 && k2 >= 128);
-  const int bm = big ? 128 : 64;
-  const int bn = big ? 128 : 64;
-  const int tiles = ((n + bm - 1) / bm) * ((k2 + bn - 1) / bn);
-  int slices = 1;
-  while (!pertgnn_deterministic() && tiles * slices < 512 && slices < 64 &&
-         (long)slices * 64 * 4 < m)
-    slices *= 2;
+  const bool big = gemm_dispatch::tn_tile128(n, k2);
+  const int tiles = gemm_dispatch::tn_tiles(n, k2);
+  const int slices =
+      gemm_dispatch::tn_slices(m, tiles, 64, pertgnn_deterministic());
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
@@ -613,7 +610,7 @@ void launch_gemm_bf16_tn(const float* a, const float* b, float* c,
 void launch_gemm_fp16_nt(const float* a, const float* b, const float* bias,
                          float* c, int m, int n, int k, bool relu,
                          hipStream_t s) {
-  if (m >= 512 && n >= 128) {
+  if (gemm_dispatch::tile128(m, n)) {
     const int grid = ((m + 127) / 128) * ((n + 127) / 128);
     gemm_bf16_nt_kernel<128, 128, 32, _Float16>
         <<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(a, b, bias, c, m, n, k,
@@ -629,7 +626,7 @@ void launch_gemm_fp16_nt(const float* a, const float* b, const float* bias,
 void launch_gemm_fp16_nn(const float* a, const float* b, const float* bias,
                          float* c, int m, int n, int k2, bool relu,
                          hipStream_t s) {
-  if (m >= 512 && k2 >= 128) {
+  if (gemm_dispatch::tile128(m, k2)) {
     const int grid = ((m + 127) / 128) * ((k2 + 127) / 128);
     gemm_bf16_nn_kernel<128, 128, 32, _Float16>
         <<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(a, b, bias, c, m, n, k2,
@@ -644,14 +641,10 @@ void launch_gemm_fp16_nn(const float* a, const float* b, const float* bias,
 
 void launch_gemm_fp16_tn(const float* a, const float* b, float* c,
                          float* dbias, int m, int n, int k2, hipStream_t s) {
-  const bool big = (n >= 128 && k2 >= 128);
-  const int bm = big ? 128 : 64;
-  const int bn = big ? 128 : 64;
-  const int tiles = ((n + bm - 1) / bm) * ((k2 + bn - 1) / bn);
-  int slices = 1;
-  while (!pertgnn_deterministic() && tiles * slices < 512 && slices < 64 &&
-         (long)slices * 64 * 4 < m)
-    slices *= 2;
+  const bool big = gemm_dispatch::tn_tile128(n, k2);
+  const int tiles = gemm_dispatch::tn_tiles(n, k2);
+  const int slices =
+      gemm_dispatch::tn_slices(m, tiles, 64, pertgnn_deterministic());
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
@@ -677,7 +670,7 @@ void launch_gemm_fp16_tn(const float* a, const float* b, float* c,
 void launch_gemm_bf16_nt_o16(const float* a, const float* b, const float* bias,
                              void* c_v, int m, int n, int k, hipStream_t s) {
   __bf16* c = (__bf16*)c_v;
-  if (m >= 512 && n >= 128) {
+  if (gemm_dispatch::tile128(m, n)) {
     const int grid = ((m + 127) / 128) * ((n + 127) / 128);
     gemm_bf16_nt_kernel<128, 128, 32, __bf16, float, __bf16>
         <<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(a, b, bias, c, m, n, k, 0);
@@ -691,7 +684,7 @@ void launch_gemm_bf16_nt_o16(const float* a, const float* b, const float* bias,
 void launch_gemm_bf16_nn_a16(const void* a_v, const float* b, float* c, int m,
                              int n, int k2, hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
-  if (m >= 512 && k2 >= 128) {
+  if (gemm_dispatch::tile128(m, k2)) {
     const int grid = ((m + 127) / 128) * ((k2 + 127) / 128);
     gemm_bf16_nn_kernel<128, 128, 32, __bf16, __bf16, float>
         <<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(a, b, nullptr, c, m, n, k2,
@@ -708,14 +701,10 @@ void launch_gemm_bf16_tn_a16(const void* a_v, const float* b, float* c,
                              float* dbias, int m, int n, int k2,
                              hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
-  const bool big = (n >= 128 && k2 >= 128);
-  const int bm = big ? 128 : 64;
-  const int bn = big ? 128 : 64;
-  const int tiles = ((n + bm - 1) / bm) * ((k2 + bn - 1) / bn);
-  int slices = 1;
-  while (!pertgnn_deterministic() && tiles * slices < 512 && slices < 64 &&
-         (long)slices * 64 * 4 < m)
-    slices *= 2;
+  const bool big = gemm_dispatch::tn_tile128(n, k2);
+  const int tiles = gemm_dispatch::tn_tiles(n, k2);
+  const int slices =
+      gemm_dispatch::tn_slices(m, tiles, 64, pertgnn_deterministic());
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
@@ -744,7 +733,7 @@ void launch_gemm_bf16_nt_a16o16(const void* a_v, const float* b,
                                 int k, hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
   __bf16* c = (__bf16*)c_v;
-  if (m >= 512 && n >= 128) {
+  if (gemm_dispatch::tile128(m, n)) {
     const int grid = ((m + 127) / 128) * ((n + 127) / 128);
     if (gemm_t512()) {
       gemm_bf16_nt_kernel<128, 128, 32, __bf16, __bf16, __bf16, 512>
@@ -764,7 +753,7 @@ void launch_gemm_bf16_nn_a16o16(const void* a_v, const float* b, void* c_v,
                                 int m, int n, int k2, hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
   __bf16* c = (__bf16*)c_v;
-  if (m >= 512 && k2 >= 128) {
+  if (gemm_dispatch::tile128(m, k2)) {
     const int grid = ((m + 127) / 128) * ((k2 + 127) / 128);
     if (gemm_t512()) {
       gemm_bf16_nn_kernel<128, 128, 32, __bf16, __bf16, __bf16, 512>
@@ -787,14 +776,10 @@ void launch_gemm_bf16_tn_a16b16(const void* a_v, const void* b_v, float* c,
                                 hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
   const __bf16* b = (const __bf16*)b_v;
-  const bool big = (n >= 128 && k2 >= 128);
-  const int bm = big ? 128 : 64;
-  const int bn = big ? 128 : 64;
-  const int tiles = ((n + bm - 1) / bm) * ((k2 + bn - 1) / bn);
-  int slices = 1;
-  while (!pertgnn_deterministic() && tiles * slices < 512 && slices < 64 &&
-         (long)slices * 64 * 4 < m)
-    slices *= 2;
+  const bool big = gemm_dispatch::tn_tile128(n, k2);
+  const int tiles = gemm_dispatch::tn_tiles(n, k2);
+  const int slices =
+      gemm_dispatch::tn_slices(m, tiles, 64, pertgnn_deterministic());
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
@@ -824,7 +809,7 @@ void launch_gemm_fp16_nt_a16o16(const void* a_v, const float* b,
                                 int k, hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
   __bf16* c = (__bf16*)c_v;
-  if (m >= 512 && n >= 128) {
+  if (gemm_dispatch::tile128(m, n)) {
     const int grid = ((m + 127) / 128) * ((n + 127) / 128);
     gemm_bf16_nt_kernel<128, 128, 32, _Float16, __bf16, __bf16>
         <<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(a, b, bias, c, m, n, k, 0);
@@ -839,7 +824,7 @@ void launch_gemm_fp16_nn_a16o16(const void* a_v, const float* b, void* c_v,
                                 int m, int n, int k2, hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
   __bf16* c = (__bf16*)c_v;
-  if (m >= 512 && k2 >= 128) {
+  if (gemm_dispatch::tile128(m, k2)) {
     const int grid = ((m + 127) / 128) * ((k2 + 127) / 128);
     gemm_bf16_nn_kernel<128, 128, 32, _Float16, __bf16, __bf16>
         <<<dim3(grid), dim3(BGEMM_THREADS), 0, s>>>(a, b, nullptr, c, m, n, k2,
@@ -857,14 +842,10 @@ void launch_gemm_fp16_tn_a16b16(const void* a_v, const void* b_v, float* c,
                                 hipStream_t s) {
   const __bf16* a = (const __bf16*)a_v;
   const __bf16* b = (const __bf16*)b_v;
-  const bool big = (n >= 128 && k2 >= 128);
-  const int bm = big ? 128 : 64;
-  const int bn = big ? 128 : 64;
-  const int tiles = ((n + bm - 1) / bm) * ((k2 + bn - 1) / bn);
-  int slices = 1;
-  while (!pertgnn_deterministic() && tiles * slices < 512 && slices < 64 &&
-         (long)slices * 64 * 4 < m)
-    slices *= 2;
+  const bool big = gemm_dispatch::tn_tile128(n, k2);
+  const int tiles = gemm_dispatch::tn_tiles(n, k2);
+  const int slices =
+      gemm_dispatch::tn_slices(m, tiles, 64, pertgnn_deterministic());
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
@@ -1187,7 +1168,7 @@ void launch_gemm_a16_glds_nt(const void* a_v, const void* b16_v,
   constexpr int BM = 128, BN = 128;
   if (m <= 0) return;
   const int mt = (m + BM - 1) / BM;  // row tiles, the partial last one included
-  if (m / BM >= 1024 && n == 256 && k % 32 == 0 && glds_n256()) {
+  if (gemm_dispatch::glds_nt_wide(m, n, k) && glds_n256()) {
     // single-column-tile variant for the dgrad shape: A is streamed exactly
     // once and the per-block K-loop halves its barrier count (measured
     // +12% at [180k,1024]x[1024,256]); needs >= ~1024 full row tiles to fill
@@ -1444,10 +1425,7 @@ void launch_gemm_a16_glds_tn(const void* a_v, const void* b_v, float* c,
   const int tiles = (n / BM) * (k2 / BN);
   // split-K over the full BKM steps; the tail step rides the last slice and
   // does not change the split (m and m - m % BKM slice alike)
-  int slices = 1;
-  while (tiles * slices < 512 && slices < 64 &&
-         (long)slices * BKM * 4 < m - m % BKM)
-    slices *= 2;
+  const int slices = gemm_dispatch::glds_tn_slices(m, tiles);
   const long nc = (long)n * k2;
   if (dbias == c + nc) {
     HIP_CHECK(hipMemsetAsync(c, 0, (nc + n) * sizeof(float), s));

@@ -1,0 +1,75 @@
+// Host-only dispatch predicates of the linear / GEMM paths.  The launchers in
+// gemm.hip and gemm_bf16.hip, the linear_* bindings and the linear_path()
+// binding all decide through these, so what linear_path() reports is what
+// runs.  Plain C++: no device code, no HIP call, no environment read (the
+// callers pass PERTGNN_DETERMINISTIC in; the experiment knobs stay with the
+// launchers and are assumed at their defaults by linear_path()).
+//
+// Shapes follow the torch Linear layout: x [m, k], w [n, k], y / g [m, n].
+#pragma once
+
+namespace gemm_dispatch {
+
+// NT / NN kernels with register (or fp32) staging: the 128x128 tile for big
+// shapes, 64x64 otherwise.  `cols` is the output width (n forward, k dgrad).
+inline bool tile128(int m, int cols) { return m >= 512 && cols >= 128; }
+
+// TN (wgrad) kernels with register (or fp32) staging: tile by the output
+inline bool tn_tile128(int n, int k2) { return n >= 128 && k2 >= 128; }
+
+inline int tn_tiles(int n, int k2) {
+  const int b = tn_tile128(n, k2) ? 128 : 64;
+  return ((n + b - 1) / b) * ((k2 + b - 1) / b);
+}
+
+// split-K slice count of those TN kernels: double while the grid is under
+// 512 blocks and every slice keeps at least four K steps of `step` rows
+// (32 for the fp32 kernel, 64 for the 16-bit ones); one slice when
+// deterministic.
+inline int tn_slices(int m, int tiles, int step, bool deterministic) {
+  int slices = 1;
+  while (!deterministic && tiles * slices < 512 && slices < 64 &&
+         (long)slices * step * 4 < m)
+    slices *= 2;
+  return slices;
+}
+
+// forward on the glds NT kernel: full 128-wide column tiles, full K steps of
+// 32 (which also makes the rows 16-B aligned)
+inline bool fwd_glds_ok(int m, int n, int k) {
+  return m >= 512 && n % 128 == 0 && k % 32 == 0;
+}
+
+// dgrad as glds NT over the transposed weight image (contraction n, width k);
+// shared with the forward so that it can hand the image over
+inline bool dgrad_glds_ok(int m, int n, int k) {
+  return m >= 512 && k % 128 == 0 && n % 64 == 0;
+}
+
+// wgrad on the glds TN kernel; its split-K adds atomically, so not in the
+// deterministic mode
+inline bool wgrad_glds_ok(int m, int n, int k, bool deterministic) {
+  return !deterministic && m >= 512 && n % 128 == 0 && k % 128 == 0;
+}
+
+// 128x256 single-column-tile variant of the glds NT kernel (`cols` is the
+// output width, `contract` the contraction length)
+inline bool glds_nt_wide(int m, int cols, int contract) {
+  return m / 128 >= 1024 && cols == 256 && contract % 32 == 0;
+}
+
+// split-K slice count of the glds TN kernel (K steps of 64 rows; the m % 64
+// tail rides the last non-empty slice and does not change the split)
+inline int glds_tn_slices(int m, int tiles) {
+  constexpr int BKM = 64;
+  int slices = 1;
+  while (tiles * slices < 512 && slices < 64 &&
+         (long)slices * BKM * 4 < m - m % BKM)
+    slices *= 2;
+  return slices;
+}
+
+// one-wave-per-strip NN kernel for the tiny-row dgrad (fp32 x, bf16 g)
+inline bool dgrad_skinny(int m) { return m <= 16; }
+
+}  // namespace gemm_dispatch
