@@ -4,6 +4,7 @@
 
 #include <climits>
 #include <cstdlib>
+#include <memory>
 #include <optional>
 #include <string>
 #include <vector>
@@ -21,6 +22,58 @@ namespace {
 
 inline hipStream_t cur_stream() {
   return (hipStream_t)c10::cuda::getCurrentCUDAStream().stream();
+}
+
+using OptTensor = std::optional<torch::Tensor>;
+
+// A gradient sink is the optimizer's fp32 flat-gradient slice of a parameter,
+// handed to a backward op as the destination of that parameter's gradient:
+// the op ADDS into it (plain read-modify-write where one thread owns the
+// element, atomicAdd where several combine) and never clears or stores, so
+// the result is what autograd's accumulation of a returned gradient would
+// have left there.  A sink is only 4-byte aligned (flat offsets are sums of
+// numel()) and sits between other parameters' gradients: the epilogues that
+// write one are scalar.  -> its pointer, or nullptr if there is none; a sink
+// of the wrong kind is an error, never a silent fall-back.
+inline float* grad_sink(const OptTensor& sink, const torch::Tensor& like,
+                        at::IntArrayRef shape, const char* what) {
+  if (!sink.has_value() || !sink->defined()) return nullptr;
+  TORCH_CHECK(sink->is_cuda() && sink->device() == like.device(), what,
+              ": the gradient sink must be on the op's GPU");
+  TORCH_CHECK(sink->scalar_type() == torch::kFloat32, what,
+              ": the gradient sink must be float32");
+  TORCH_CHECK(sink->is_contiguous(), what,
+              ": the gradient sink must be contiguous");
+  TORCH_CHECK(sink->sizes() == shape, what, ": the gradient sink must be ",
+              shape, ", got ", sink->sizes());
+  return sink->data_ptr<float>();
+}
+
+// dgamma/dbeta of a BN backward: both sinks or neither
+struct BnAffineOut {
+  torch::Tensor dgamma, dbeta;  // what the op returns ([0] when sunk)
+  float* pg;
+  float* pb;
+  bool acc;
+};
+inline BnAffineOut bn_affine_out(const OptTensor& dgamma_sink,
+                                 const OptTensor& dbeta_sink,
+                                 const torch::Tensor& like, int h,
+                                 const char* what) {
+  BnAffineOut o;
+  o.pg = grad_sink(dgamma_sink, like, {h}, what);
+  o.pb = grad_sink(dbeta_sink, like, {h}, what);
+  TORCH_CHECK((o.pg != nullptr) == (o.pb != nullptr), what,
+              ": dgamma and dbeta sinks come together");
+  o.acc = o.pg != nullptr;
+  auto fopt = like.options().dtype(torch::kFloat32);
+  o.dgamma = torch::empty({o.acc ? 0 : h}, fopt);
+  o.dbeta = torch::empty({o.acc ? 0 : h}, fopt);
+  if (!o.acc) {
+    o.pg = o.dgamma.data_ptr<float>();
+    o.pb = o.dbeta.data_ptr<float>();
+  }
+  return o;
 }
 
 }  // namespace
@@ -60,7 +113,8 @@ void launch_bn_fwd(const float*, const float*, const float*, float*, float*,
 void launch_counter_bump(unsigned long long*, hipStream_t);
 void launch_bn_bwd(const float*, const float*, const float*, const float*,
                    const float*, const float*, float*, float*, float*, float*,
-                   long, int, bool, float, float*, hipStream_t);
+                   long, int, bool, float, float*, hipStream_t,
+                   bool acc = false);
 void launch_bn_stats_only(const float*, long, int, float*, float*,
                           hipStream_t);
 void launch_bn_finalize_apply(const float*, const float*, const float*,
@@ -75,7 +129,10 @@ void launch_bn_bwd_apply_only(const float*, const float*, const float*,
                               const float*, const float*, const float*,
                               const float*, const float*, float*, long, int,
                               bool, float, hipStream_t);
-void launch_bn_grad_affine(const float*, float*, float*, int, hipStream_t);
+// trailing `bool acc` of a backward launcher: its parameter-gradient outputs
+// are gradient sinks (see grad_sink below), added to and never cleared
+void launch_bn_grad_affine(const float*, float*, float*, int, hipStream_t,
+                           bool acc = false);
 // act16 variants (bf16 x/y/g/dx streams, fp32 statistics)
 void launch_bn_stats_only16(const void*, long, int, float*, float*,
                             hipStream_t);
@@ -100,7 +157,7 @@ void launch_bn_bwd_apply_only16(const void*, const void*, const void*,
 void launch_bn_bwd16(const void*, const void*, const void*, const float*,
                      const float*, const float*, float*, void*, float*,
                      float*, long, int, bool, float, float*,
-                     const unsigned char*, hipStream_t);
+                     const unsigned char*, hipStream_t, bool acc = false);
 void launch_seg_pool_fwd16(const void*, const float*, const float*,
                            const int*, float*, float*, int, int, int,
                            hipStream_t);
@@ -111,13 +168,13 @@ void launch_gemm_bf16_nt_a16o16(const void*, const float*, const float*,
 void launch_gemm_bf16_nn_a16o16(const void*, const float*, void*, int, int,
                                 int, hipStream_t);
 void launch_gemm_bf16_tn_a16b16(const void*, const void*, float*, float*, int,
-                                int, int, hipStream_t);
+                                int, int, hipStream_t, bool acc = false);
 void launch_gemm_fp16_nt_a16o16(const void*, const float*, const float*,
                                 void*, int, int, int, hipStream_t);
 void launch_gemm_fp16_nn_a16o16(const void*, const float*, void*, int, int,
                                 int, hipStream_t);
 void launch_gemm_fp16_tn_a16b16(const void*, const void*, float*, float*, int,
-                                int, int, hipStream_t);
+                                int, int, hipStream_t, bool acc = false);
 void launch_quantile_loss_fwd(const float*, const float*, float*, long, float,
                               hipStream_t);
 void launch_quantile_loss_bwd(const float*, const float*, const float*, float*,
@@ -183,7 +240,8 @@ void launch_edge_attn_fused_bwd16(const void*, int, const void*,
 void launch_bn_bwd_partials_affine16(const void*, const void*,
                                      const unsigned char*, const float*,
                                      const float*, long, int, float*, float,
-                                     float*, float*, float*, hipStream_t);
+                                     float*, float*, float*, hipStream_t,
+                                     bool acc = false);
 void launch_edge_attn_fused_infer(const float*, const float*, const float*,
                                   const long*, int, const int*, const int*,
                                   const float*, const float*, int, float*,
@@ -203,23 +261,24 @@ void launch_convert_w16(const float*, void*, long, hipStream_t);
 void launch_convert_w16_both(const float*, void*, void*, int, int,
                              hipStream_t);
 void launch_gemm_a16_glds_tn(const void*, const void*, float*, float*, int,
-                             int, int, hipStream_t);
+                             int, int, hipStream_t, bool acc = false);
 void launch_transpose_convert_w16(const float*, void*, int, int, hipStream_t);
 void launch_gemm_skinny_nn(const void*, const float*, float*, int, int, int,
                            hipStream_t);
 void launch_gemm_bf16_nn_a16(const void*, const float*, float*, int, int, int,
                              hipStream_t);
 void launch_gemm_bf16_tn_a16(const void*, const float*, float*, float*, int,
-                             int, int, hipStream_t);
+                             int, int, hipStream_t, bool acc = false);
 // grouped P-table GEMMs (all layers, both tables, one launch each)
 int ptables_max_groups();
 void launch_ptables_fwd(int, const float* const*, const float* const*,
                         void* const*, const int*, int, int, hipStream_t);
 void launch_ptables_dgrad(const void* const*, const float* const*, const int*,
-                          float* const*, const int*, int, int, bool,
+                          float* const*, const int*, int, int, const bool*,
                           hipStream_t);
 bool launch_ptables_wgrad(int, const void* const*, const float* const*,
-                          float* const*, const int*, int, bool, hipStream_t);
+                          float* const*, const int*, int, bool, hipStream_t,
+                          const bool* sink = nullptr);
 std::vector<torch::Tensor> collate_native(
     std::vector<torch::Tensor>, std::vector<torch::Tensor>,
     std::vector<torch::Tensor>, std::vector<torch::Tensor>,
@@ -428,22 +487,22 @@ std::vector<torch::Tensor> bn_relu_fwd(torch::Tensor x, torch::Tensor gamma,
 std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor g, torch::Tensor x,
                                        torch::Tensor gamma, torch::Tensor mean,
                                        torch::Tensor invstd, torch::Tensor y,
-                                       bool relu, double keep_inv = 1.0) {
+                                       bool relu, double keep_inv = 1.0,
+                                       OptTensor dgamma_sink = std::nullopt,
+                                       OptTensor dbeta_sink = std::nullopt) {
   CHECK_IN(g); CHECK_IN(x);
   const long n = x.size(0);
   const int h = x.size(1);
   auto dx = torch::empty_like(x);
-  auto dgamma = torch::empty({h}, x.options());
-  auto dbeta = torch::empty({h}, x.options());
+  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, "bn_relu_bwd");
   auto partials = torch::empty({2 * h}, x.options());
   auto slab = bn_wide_slab(x);
   launch_bn_bwd(g.data_ptr<float>(), x.data_ptr<float>(), y.data_ptr<float>(),
                 mean.data_ptr<float>(), invstd.data_ptr<float>(),
                 gamma.data_ptr<float>(), partials.data_ptr<float>(),
-                dx.data_ptr<float>(), dgamma.data_ptr<float>(),
-                dbeta.data_ptr<float>(), n, h, relu, (float)keep_inv,
-                bn_slab_ptr(slab), cur_stream());
-  return {dx, dgamma, dbeta};
+                dx.data_ptr<float>(), aff.pg, aff.pb, n, h, relu,
+                (float)keep_inv, bn_slab_ptr(slab), cur_stream(), aff.acc);
+  return {dx, aff.dgamma, aff.dbeta};
 }
 
 torch::Tensor quantile_loss_fwd(torch::Tensor y, torch::Tensor y_hat,
@@ -1053,15 +1112,16 @@ std::vector<torch::Tensor> bn_bwd_apply(torch::Tensor g, torch::Tensor x,
                                         torch::Tensor gamma,
                                         torch::Tensor partials_global,
                                         torch::Tensor partials_local,
-                                        bool relu, double keep_inv = 1.0) {
+                                        bool relu, double keep_inv = 1.0,
+                                        OptTensor dgamma_sink = std::nullopt,
+                                        OptTensor dbeta_sink = std::nullopt) {
   CHECK_IN(g); CHECK_IN(x);
   const int h = x.size(1);
   TORCH_CHECK(partials_global.numel() == 2 * h + 1,
               "bn_bwd_apply expects [2h+1] partials with the global count "
               "in the tail slot");
   auto dx = torch::empty_like(x);
-  auto dgamma = torch::empty({h}, x.options());
-  auto dbeta = torch::empty({h}, x.options());
+  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, "bn_bwd_apply");
   launch_bn_bwd_apply_only(g.data_ptr<float>(), x.data_ptr<float>(),
                            y.data_ptr<float>(), mean.data_ptr<float>(),
                            invstd.data_ptr<float>(), gamma.data_ptr<float>(),
@@ -1069,10 +1129,9 @@ std::vector<torch::Tensor> bn_bwd_apply(torch::Tensor g, torch::Tensor x,
                            partials_global.data_ptr<float>() + 2 * h,
                            dx.data_ptr<float>(), x.size(0), h, relu,
                            (float)keep_inv, cur_stream());
-  launch_bn_grad_affine(partials_local.data_ptr<float>(),
-                        dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), h,
-                        cur_stream());
-  return {dx, dgamma, dbeta};
+  launch_bn_grad_affine(partials_local.data_ptr<float>(), aff.pg, aff.pb, h,
+                        cur_stream(), aff.acc);
+  return {dx, aff.dgamma, aff.dbeta};
 }
 
 // split backward entry points so python can overlap dgrad (current stream)
@@ -1183,12 +1242,27 @@ torch::Tensor linear_dgrad16(torch::Tensor g, torch::Tensor w) {
   return dx;
 }
 
+// dw_sink / db_sink (here and in linear_wgrad16_b16): gradient sinks of w
+// and b.  With dw_sink the op adds dw (and db, whose sink must then come
+// along when has_bias) into them and returns two empty tensors.
 std::vector<torch::Tensor> linear_wgrad16(torch::Tensor g, torch::Tensor x,
-                                          bool has_bias) {
+                                          bool has_bias,
+                                          OptTensor dw_sink = std::nullopt,
+                                          OptTensor db_sink = std::nullopt) {
   CHECK_IN(g); CHECK_IN(x);
   const int m = x.size(0);
   const int k = x.size(1);
   const int n = g.size(1);
+  float* dw_s = grad_sink(dw_sink, x, {n, k}, "linear_wgrad16");
+  float* db_s = grad_sink(db_sink, x, {n}, "linear_wgrad16");
+  TORCH_CHECK((db_s != nullptr) == (dw_s != nullptr && has_bias),
+              "linear_wgrad16: a db sink comes with a dw sink and a bias");
+  if (dw_s) {
+    if (m > 0)  // no rows: nothing to add
+      launch_gemm_bf16_tn_a16(g.data_ptr(), x.data_ptr<float>(), dw_s, db_s, m,
+                              n, k, cur_stream(), /*acc=*/true);
+    return {torch::empty({0}, x.options()), torch::empty({0}, x.options())};
+  }
   if (m == 0)  // no rows: the sums over them are zero, nothing to launch
     return {torch::zeros({n, k}, x.options()),
             torch::zeros({has_bias ? n : 0}, x.options())};
@@ -1247,23 +1321,23 @@ std::vector<torch::Tensor> bn_relu_bwd16(torch::Tensor g, torch::Tensor x,
                                          torch::Tensor gamma,
                                          torch::Tensor mean,
                                          torch::Tensor invstd, torch::Tensor y,
-                                         bool relu, double keep_inv = 1.0) {
+                                         bool relu, double keep_inv = 1.0,
+                                         OptTensor dgamma_sink = std::nullopt,
+                                         OptTensor dbeta_sink = std::nullopt) {
   CHECK_IN(g); CHECK_IN(x);
   const long n = x.size(0);
   const int h = x.size(1);
   auto fopt = x.options().dtype(torch::kFloat32);
   auto dx = torch::empty_like(x);
-  auto dgamma = torch::empty({h}, fopt);
-  auto dbeta = torch::empty({h}, fopt);
+  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, "bn_relu_bwd16");
   auto partials = torch::empty({2 * h}, fopt);
   auto slab = bn_wide_slab(x);
   launch_bn_bwd16(g.data_ptr(), x.data_ptr(), y.data_ptr(),
                   mean.data_ptr<float>(), invstd.data_ptr<float>(),
                   gamma.data_ptr<float>(), partials.data_ptr<float>(),
-                  dx.data_ptr(), dgamma.data_ptr<float>(),
-                  dbeta.data_ptr<float>(), n, h, relu, (float)keep_inv,
-                  bn_slab_ptr(slab), bn_mask_ptr(y, x), cur_stream());
-  return {dx, dgamma, dbeta};
+                  dx.data_ptr(), aff.pg, aff.pb, n, h, relu, (float)keep_inv,
+                  bn_slab_ptr(slab), bn_mask_ptr(y, x), cur_stream(), aff.acc);
+  return {dx, aff.dgamma, aff.dbeta};
 }
 
 std::vector<torch::Tensor> bn_finalize_apply16(
@@ -1318,16 +1392,16 @@ torch::Tensor bn_bwd_partials16(torch::Tensor g, torch::Tensor x,
 std::vector<torch::Tensor> bn_bwd_apply16(
     torch::Tensor g, torch::Tensor x, torch::Tensor y, torch::Tensor mean,
     torch::Tensor invstd, torch::Tensor gamma, torch::Tensor partials_global,
-    torch::Tensor partials_local, bool relu, double keep_inv = 1.0) {
+    torch::Tensor partials_local, bool relu, double keep_inv = 1.0,
+    OptTensor dgamma_sink = std::nullopt,
+    OptTensor dbeta_sink = std::nullopt) {
   CHECK_IN(g); CHECK_IN(x);
   const int h = x.size(1);
   TORCH_CHECK(partials_global.numel() == 2 * h + 1,
               "bn_bwd_apply16 expects [2h+1] partials with the global count "
               "in the tail slot");
-  auto fopt = x.options().dtype(torch::kFloat32);
   auto dx = torch::empty_like(x);
-  auto dgamma = torch::empty({h}, fopt);
-  auto dbeta = torch::empty({h}, fopt);
+  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, "bn_bwd_apply16");
   launch_bn_bwd_apply_only16(g.data_ptr(), x.data_ptr(), y.data_ptr(),
                              mean.data_ptr<float>(), invstd.data_ptr<float>(),
                              gamma.data_ptr<float>(),
@@ -1335,10 +1409,9 @@ std::vector<torch::Tensor> bn_bwd_apply16(
                              partials_global.data_ptr<float>() + 2 * h,
                              dx.data_ptr(), x.size(0), h, relu,
                              (float)keep_inv, bn_mask_ptr(y, x), cur_stream());
-  launch_bn_grad_affine(partials_local.data_ptr<float>(),
-                        dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), h,
-                        cur_stream());
-  return {dx, dgamma, dbeta};
+  launch_bn_grad_affine(partials_local.data_ptr<float>(), aff.pg, aff.pb, h,
+                        cur_stream(), aff.acc);
+  return {dx, aff.dgamma, aff.dbeta};
 }
 
 // Backward of "fused attention forward -> BN+ReLU(+dropout) forward" in act16
@@ -1357,7 +1430,9 @@ std::vector<torch::Tensor> edge_attn_bn_bwd16(
     torch::Tensor csr_src, torch::Tensor col_ptr, torch::Tensor csc_dst,
     torch::Tensor csc_eid, int64_t heads = 1,
     std::optional<torch::Tensor> partials_global_opt = std::nullopt,
-    std::optional<torch::Tensor> partials_local_opt = std::nullopt) {
+    std::optional<torch::Tensor> partials_local_opt = std::nullopt,
+    OptTensor dgamma_sink = std::nullopt,
+    OptTensor dbeta_sink = std::nullopt) {
   CHECK_IN(g); CHECK_IN(x); CHECK_IN(qkvs); CHECK_IN(alpha); CHECK_IN(mask);
   CHECK_IN(gamma); CHECK_IN(mean); CHECK_IN(invstd);
   const int n = qkvs.size(0);
@@ -1395,8 +1470,8 @@ std::vector<torch::Tensor> edge_attn_bn_bwd16(
     partials_local = *partials_local_opt;
   }
   auto fopt = qkvs.options().dtype(torch::kFloat32);
-  auto dgamma = torch::empty({h}, fopt);
-  auto dbeta = torch::empty({h}, fopt);
+  auto aff =
+      bn_affine_out(dgamma_sink, dbeta_sink, qkvs, h, "edge_attn_bn_bwd16");
   AttnBnBwd bn{};
   bn.x = x.data_ptr();
   bn.mask = bn_mask_ptr(mask, x);
@@ -1416,16 +1491,15 @@ std::vector<torch::Tensor> edge_attn_bn_bwd16(
                 "global count in the tail slot");
     bn.partials = partials_global.data_ptr<float>();
     bn.count_ptr = partials_global.data_ptr<float>() + 2 * h;
-    launch_bn_grad_affine(partials_local.data_ptr<float>(),
-                          dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), h,
-                          cur_stream());
+    launch_bn_grad_affine(partials_local.data_ptr<float>(), aff.pg, aff.pb, h,
+                          cur_stream(), aff.acc);
   } else {
     partials = torch::empty({2 * h}, fopt);
     slab = bn_wide_slab(x);
     launch_bn_bwd_partials_affine16(
         g.data_ptr(), x.data_ptr(), bn.mask, bn.mean, bn.invstd, n, h,
-        partials.data_ptr<float>(), bn.keep_inv, bn_slab_ptr(slab),
-        dgamma.data_ptr<float>(), dbeta.data_ptr<float>(), cur_stream());
+        partials.data_ptr<float>(), bn.keep_inv, bn_slab_ptr(slab), aff.pg,
+        aff.pb, cur_stream(), aff.acc);
     bn.partials = partials.data_ptr<float>();
   }
   auto dqkvs = torch::empty_like(qkvs);
@@ -1439,7 +1513,7 @@ std::vector<torch::Tensor> edge_attn_bn_bwd16(
       col_ptr.data_ptr<int>(), csc_dst.data_ptr<int>(),
       csc_eid.data_ptr<int>(), dqkvs.data_ptr(), de.data_ptr(),
       dal.data_ptr<float>(), n, h, ne, (int)heads, cur_stream(), &bn);
-  return {dqkvs, de, dgamma, dbeta};
+  return {dqkvs, de, aff.dgamma, aff.dbeta};
 }
 
 torch::Tensor seg_pool_fwd16(torch::Tensor x, torch::Tensor probs,
@@ -1594,42 +1668,51 @@ torch::Tensor linear_dgrad16_o16(torch::Tensor g, torch::Tensor w,
 
 std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
                                               bool has_bias,
-                                              bool fp16c = false) {
+                                              bool fp16c = false,
+                                              OptTensor dw_sink = std::nullopt,
+                                              OptTensor db_sink = std::nullopt) {
   CHECK_IN(g); CHECK_IN(x);
   const int m = x.size(0);
   const int k = x.size(1);
   const int n = g.size(1);
   auto fopt = x.options().dtype(torch::kFloat32);
-  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
+  float* dw_ptr = grad_sink(dw_sink, x, {n, k}, "linear_wgrad16_b16");
+  float* db_ptr = grad_sink(db_sink, x, {n}, "linear_wgrad16_b16");
+  const bool acc = dw_ptr != nullptr;
+  TORCH_CHECK((db_ptr != nullptr) == (acc && has_bias),
+              "linear_wgrad16_b16: a db sink comes with a dw sink and a bias");
+  torch::Tensor dw = torch::empty({0}, fopt), db = torch::empty({0}, fopt);
+  if (m == 0) {  // no rows: the sums over them are zero, nothing to launch
+    if (acc) return {dw, db};
     return {torch::zeros({n, k}, fopt), torch::zeros({has_bias ? n : 0}, fopt)};
-  // dw and db are views of one buffer, so the glds path clears both with a
-  // single memset (the other paths clear the two views on their own)
-  const long nk = (long)n * k;
-  auto buf = torch::empty({nk + (has_bias ? n : 0)}, fopt);
-  auto dw = buf.narrow(0, 0, nk).view({n, k});
-  torch::Tensor db = torch::empty({0}, fopt);
-  float* db_ptr = nullptr;
-  if (has_bias) {
-    db = buf.narrow(0, nk, n);
-    db_ptr = db.data_ptr<float>();
+  }
+  if (!acc) {
+    // dw and db are views of one buffer, so the glds path clears both with a
+    // single memset (the other paths clear the two views on their own)
+    const long nk = (long)n * k;
+    auto buf = torch::empty({nk + (has_bias ? n : 0)}, fopt);
+    dw = buf.narrow(0, 0, nk).view({n, k});
+    dw_ptr = dw.data_ptr<float>();
+    if (has_bias) {
+      db = buf.narrow(0, nk, n);
+      db_ptr = db.data_ptr<float>();
+    }
   }
   if (fp16c) {
-    launch_gemm_fp16_tn_a16b16(g.data_ptr(), x.data_ptr(),
-                               dw.data_ptr<float>(), db_ptr, m, n, k,
-                               cur_stream());
+    launch_gemm_fp16_tn_a16b16(g.data_ptr(), x.data_ptr(), dw_ptr, db_ptr, m,
+                               n, k, cur_stream(), acc);
     return {dw, db};
   }
   // glds TN fast path (panel-major images + ds_read_b64_tr_b16 fragments);
   // split-K atomics => not for the deterministic mode
   const char* det = getenv("PERTGNN_DETERMINISTIC");
   if (gemm_dispatch::wgrad_glds_ok(m, n, k, det && det[0] == '1')) {
-    launch_gemm_a16_glds_tn(g.data_ptr(), x.data_ptr(), dw.data_ptr<float>(),
-                            db_ptr, m, n, k, cur_stream());
+    launch_gemm_a16_glds_tn(g.data_ptr(), x.data_ptr(), dw_ptr, db_ptr, m, n,
+                            k, cur_stream(), acc);
     return {dw, db};
   }
-  launch_gemm_bf16_tn_a16b16(g.data_ptr(), x.data_ptr(),
-                             dw.data_ptr<float>(), db_ptr, m, n, k,
-                             cur_stream());
+  launch_gemm_bf16_tn_a16b16(g.data_ptr(), x.data_ptr(), dw_ptr, db_ptr, m, n,
+                             k, cur_stream(), acc);
   return {dw, db};
 }
 
@@ -1799,22 +1882,44 @@ std::vector<torch::Tensor> ptables_fwd(torch::Tensor ifc_table,
 // accumulation; dW[g] of a missing dP[g] is zero.  dgrad_splits > 1 splits
 // the dgrad's layer sum over that many blocks (atomics; ignored under
 // PERTGNN_DETERMINISTIC=1, like the wgrad's split-K).
+// Gradient sinks: d_ifc_sink / d_rpc_sink for the two tables, dw_sinks empty
+// (none) or 2L entries in dP's order, each a sink or None.  An output with a
+// sink is added into it and left out of the buffer: its table slot of the
+// result is an empty tensor, and dW holds only the groups WITHOUT a sink, in
+// order.  The sink of a missing dP[g] is not touched; with every output sunk
+// nothing is allocated or cleared.
 std::vector<torch::Tensor> ptables_bwd(std::vector<torch::Tensor> dP,
                                        torch::Tensor ifc_table,
                                        torch::Tensor rpc_table,
                                        std::vector<torch::Tensor> we_ifc,
                                        std::vector<torch::Tensor> we_rpc,
-                                       int64_t dgrad_splits) {
+                                       int64_t dgrad_splits,
+                                       OptTensor d_ifc_sink = std::nullopt,
+                                       OptTensor d_rpc_sink = std::nullopt,
+                                       std::vector<OptTensor> dw_sinks = {}) {
   const int h = ptables_check(ifc_table, rpc_table, we_ifc, we_rpc);
   const int layers = (int)we_ifc.size();
   TORCH_CHECK((int)dP.size() == 2 * layers, "ptables_bwd: need ", 2 * layers,
               " dP entries, got ", dP.size());
+  TORCH_CHECK(dw_sinks.empty() || (int)dw_sinks.size() == 2 * layers,
+              "ptables_bwd: need no or ", 2 * layers, " dw_sinks entries, got ",
+              dw_sinks.size());
   const int64_t rows[2] = {ifc_table.size(0), rpc_table.size(0)};
+  float* const sink_t[2] = {
+      grad_sink(d_ifc_sink, ifc_table, {rows[0], h}, "ptables_bwd"),
+      grad_sink(d_rpc_sink, ifc_table, {rows[1], h}, "ptables_bwd")};
+  std::vector<float*> sink_w(2 * layers, nullptr);
+  int n_ret = 0;  // dW groups without a sink: the ones returned
+  for (int g = 0; g < 2 * layers; ++g) {
+    if (!dw_sinks.empty())
+      sink_w[g] = grad_sink(dw_sinks[g], ifc_table, {h, h}, "ptables_bwd");
+    if (!sink_w[g]) ++n_ret;
+  }
   bool missing = false;
   for (int g = 0; g < 2 * layers; ++g) {
     const auto& d = dP[g];
     if (!d.defined() || d.numel() == 0) {
-      missing |= rows[g / layers] > 0;
+      missing |= rows[g / layers] > 0 && !sink_w[g];
       continue;
     }
     TORCH_CHECK(d.is_cuda() && d.device() == ifc_table.device(),
@@ -1832,51 +1937,68 @@ std::vector<torch::Tensor> ptables_bwd(std::vector<torch::Tensor> dP,
       det ? 1 : (int)std::min<int64_t>(std::max<int64_t>(dgrad_splits, 1), layers);
 
   const int64_t hh = (int64_t)h * h;
-  const int64_t n_dw = 2 * layers * hh;
-  auto buf = torch::empty({n_dw + (rows[0] + rows[1]) * h},
-                          ifc_table.options());
-  auto dW = buf.narrow(0, 0, n_dw).view({2 * layers, h, h});
-  auto d_ifc = buf.narrow(0, n_dw, rows[0] * h).view({rows[0], h});
-  auto d_rpc = buf.narrow(0, n_dw + rows[0] * h, rows[1] * h).view({rows[1], h});
+  const int64_t n_dw = n_ret * hh;
+  const int64_t n_dt[2] = {sink_t[0] ? 0 : rows[0] * h,
+                           sink_t[1] ? 0 : rows[1] * h};
+  auto buf = torch::empty({n_dw + n_dt[0] + n_dt[1]}, ifc_table.options());
+  auto none = torch::empty({0}, ifc_table.options());
+  auto dW = buf.narrow(0, 0, n_dw).view({n_ret, h, h});
+  auto d_ifc = sink_t[0] ? none
+                         : buf.narrow(0, n_dw, n_dt[0]).view({rows[0], h});
+  auto d_rpc = sink_t[1] ? none
+                         : buf.narrow(0, n_dw + n_dt[0], n_dt[1])
+                               .view({rows[1], h});
 
   std::vector<const void*> dp_w, dp_d;
   std::vector<const float*> a_w, w_d;
   std::vector<float*> dw_w;
   std::vector<int> m_w;
+  std::unique_ptr<bool[]> sunk(new bool[2 * layers]);  // per launched group
   int npairs[2] = {0, 0};
+  int ret = 0;  // index in dW of the next group without a sink
   for (int g = 0; g < 2 * layers; ++g) {
     const auto& d = dP[g];
+    float* const dw_g =
+        sink_w[g] ? sink_w[g] : buf.data_ptr<float>() + (ret++) * hh;
     if (!d.defined() || d.numel() == 0) continue;
     const int t = g / layers;
     const auto& table = t == 0 ? ifc_table : rpc_table;
     const auto& w = (t == 0 ? we_ifc : we_rpc)[g % layers];
+    sunk[dp_w.size()] = sink_w[g] != nullptr;
     dp_w.push_back(d.data_ptr());
     a_w.push_back(table.data_ptr<float>());
-    dw_w.push_back(dW.data_ptr<float>() + g * hh);
+    dw_w.push_back(dw_g);
     m_w.push_back((int)rows[t]);
     dp_d.push_back(d.data_ptr());
     w_d.push_back(w.data_ptr<float>());
     ++npairs[t];
   }
   auto s = cur_stream();
+  // only what the buffer holds is ever cleared, never a sink
   const bool zero_dw =
-      missing || launch_ptables_wgrad((int)dp_w.size(), dp_w.data(), a_w.data(),
-                                      dw_w.data(), m_w.data(), h, true, s);
-  const bool zero_dt = splits > 1;
+      n_dw > 0 &&
+      (missing ||
+       launch_ptables_wgrad((int)dp_w.size(), dp_w.data(), a_w.data(),
+                            dw_w.data(), m_w.data(), h, true, s, sunk.get()));
+  const bool zero_dt = splits > 1 && n_dt[0] + n_dt[1] > 0;
   if (zero_dw || zero_dt) {
     float* beg = buf.data_ptr<float>() + (zero_dw ? 0 : n_dw);
-    const int64_t cnt = (zero_dw ? n_dw : 0) +
-                        (zero_dt ? (rows[0] + rows[1]) * h : 0);
+    const int64_t cnt =
+        (zero_dw ? n_dw : 0) + (zero_dt ? n_dt[0] + n_dt[1] : 0);
     const hipError_t err = hipMemsetAsync(beg, 0, cnt * sizeof(float), s);
     TORCH_CHECK(err == hipSuccess, "ptables_bwd: memset failed: ",
                 hipGetErrorString(err));
   }
-  float* outs[2] = {d_ifc.data_ptr<float>(), d_rpc.data_ptr<float>()};
+  float* outs[2] = {sink_t[0] ? sink_t[0] : d_ifc.data_ptr<float>(),
+                    sink_t[1] ? sink_t[1] : d_rpc.data_ptr<float>()};
   const int ms[2] = {(int)rows[0], (int)rows[1]};
+  // splits > 1 has cleared every table output that is not a sink
+  const bool addto[2] = {sink_t[0] != nullptr || splits > 1,
+                         sink_t[1] != nullptr || splits > 1};
   launch_ptables_dgrad(dp_d.data(), w_d.data(), npairs, outs, ms, h, splits,
-                       zero_dt, s);
+                       addto, s);
   launch_ptables_wgrad((int)dp_w.size(), dp_w.data(), a_w.data(), dw_w.data(),
-                       m_w.data(), h, false, s);
+                       m_w.data(), h, false, s, sunk.get());
   return {d_ifc, d_rpc, dW};
 }
 
@@ -1885,11 +2007,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("rpc_table"), py::arg("we_ifc"), py::arg("we_rpc"));
   mod.def("ptables_bwd", &ptables_bwd, py::arg("dP"), py::arg("ifc_table"),
           py::arg("rpc_table"), py::arg("we_ifc"), py::arg("we_rpc"),
-          py::arg("dgrad_splits") = 1);
+          py::arg("dgrad_splits") = 1, py::arg("d_ifc_sink") = py::none(),
+          py::arg("d_rpc_sink") = py::none(),
+          py::arg("dw_sinks") = std::vector<OptTensor>());
   mod.def("ptables_max_groups", &ptables_max_groups);
   mod.def("linear_fwd_bf16_o16", &linear_fwd_bf16_o16);
   mod.def("linear_dgrad16", &linear_dgrad16);
-  mod.def("linear_wgrad16", &linear_wgrad16);
+  mod.def("linear_wgrad16", &linear_wgrad16, py::arg("g"), py::arg("x"),
+          py::arg("has_bias"), py::arg("dw_sink") = py::none(),
+          py::arg("db_sink") = py::none());
   mod.def("vocab_scatter_dual", &vocab_scatter_dual);
   mod.def("linear_dgrad", &linear_dgrad);
   mod.def("linear_wgrad", &linear_wgrad);
@@ -1910,7 +2036,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("bn_bwd_apply", &bn_bwd_apply, py::arg("g"), py::arg("x"),
           py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
           py::arg("partials_global"), py::arg("partials_local"),
-          py::arg("relu"), py::arg("keep_inv") = 1.0);
+          py::arg("relu"), py::arg("keep_inv") = 1.0,
+          py::arg("dgamma_sink") = py::none(),
+          py::arg("dbeta_sink") = py::none());
   mod.def("vocab_scatter", &vocab_scatter);
   mod.def("collate_native", &collate_native,
           py::call_guard<py::gil_scoped_release>());
@@ -1955,7 +2083,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("seed") = torch::Tensor());
   mod.def("bn_relu_bwd16", &bn_relu_bwd16, py::arg("g"), py::arg("x"),
           py::arg("gamma"), py::arg("mean"), py::arg("invstd"), py::arg("y"),
-          py::arg("relu"), py::arg("keep_inv") = 1.0);
+          py::arg("relu"), py::arg("keep_inv") = 1.0,
+          py::arg("dgamma_sink") = py::none(),
+          py::arg("dbeta_sink") = py::none());
   mod.def("bn_finalize_apply16", &bn_finalize_apply16, py::arg("x"),
           py::arg("partials"), py::arg("gamma"), py::arg("beta"),
           py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
@@ -1967,7 +2097,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("bn_bwd_apply16", &bn_bwd_apply16, py::arg("g"), py::arg("x"),
           py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
           py::arg("partials_global"), py::arg("partials_local"),
-          py::arg("relu"), py::arg("keep_inv") = 1.0);
+          py::arg("relu"), py::arg("keep_inv") = 1.0,
+          py::arg("dgamma_sink") = py::none(),
+          py::arg("dbeta_sink") = py::none());
   mod.def("edge_attn_bn_bwd16", &edge_attn_bn_bwd16, py::arg("g"),
           py::arg("x"), py::arg("mask"), py::arg("gamma"), py::arg("mean"),
           py::arg("invstd"), py::arg("keep_inv"), py::arg("qkvs"),
@@ -1975,7 +2107,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("alpha"), py::arg("row_ptr"), py::arg("csr_src"),
           py::arg("col_ptr"), py::arg("csc_dst"), py::arg("csc_eid"),
           py::arg("heads") = 1, py::arg("partials_global") = py::none(),
-          py::arg("partials_local") = py::none());
+          py::arg("partials_local") = py::none(),
+          py::arg("dgamma_sink") = py::none(),
+          py::arg("dbeta_sink") = py::none());
   mod.def("seg_pool_fwd16", &seg_pool_fwd16);
   mod.def("seg_pool_bwd16", &seg_pool_bwd16);
   mod.def("linear_fwd_a16o16", &linear_fwd_a16o16, py::arg("x"), py::arg("w"),
@@ -1987,7 +2121,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("w"), py::arg("fp16c") = false,
           py::arg("wt16") = py::none());
   mod.def("linear_wgrad16_b16", &linear_wgrad16_b16, py::arg("g"),
-          py::arg("x"), py::arg("has_bias"), py::arg("fp16c") = false);
+          py::arg("x"), py::arg("has_bias"), py::arg("fp16c") = false,
+          py::arg("dw_sink") = py::none(), py::arg("db_sink") = py::none());
   mod.def("linear_path", &linear_path, py::arg("op"), py::arg("m"),
           py::arg("n"), py::arg("k"), py::arg("io"), py::arg("prec"),
           py::arg("deterministic") = false);
@@ -1999,7 +2134,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("seed") = torch::Tensor());
   mod.def("bn_relu_bwd", &bn_relu_bwd, py::arg("g"), py::arg("x"),
           py::arg("gamma"), py::arg("mean"), py::arg("invstd"), py::arg("y"),
-          py::arg("relu"), py::arg("keep_inv") = 1.0);
+          py::arg("relu"), py::arg("keep_inv") = 1.0,
+          py::arg("dgamma_sink") = py::none(),
+          py::arg("dbeta_sink") = py::none());
   mod.def("quantile_loss_fwd", &quantile_loss_fwd);
   mod.def("quantile_loss_bwd", &quantile_loss_bwd);
   mod.def("eval_metrics", &eval_metrics);

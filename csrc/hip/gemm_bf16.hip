@@ -416,7 +416,7 @@ __global__ void gemm_bf16_nn_kernel(const TA* __restrict__ a,
 
 template <int BM, int BN, int BK = 64, typename T16 = __bf16,
           typename TA = float, typename TB = float,
-          int THREADS = BGEMM_THREADS>
+          int THREADS = BGEMM_THREADS, bool ACC = false>
 __launch_bounds__(THREADS)
 __global__ void gemm_bf16_tn_kernel(const TA* __restrict__ a,
                                     const TB* __restrict__ b,
@@ -491,10 +491,12 @@ __global__ void gemm_bf16_tn_kernel(const TA* __restrict__ a,
         const int row = n0 + wm + mi * 16 + frow + r;
         const int col = k0 + wn + ni * 16 + fcol;
         if (row < n && col < k2) {
-          if (slices == 1)
-            c[(long)row * k2 + col] = wt.acc[mi][ni][r];
-          else
+          if (slices != 1)
             atomicAdd(&c[(long)row * k2 + col], wt.acc[mi][ni][r]);
+          else if (ACC)  // gradient sink: this thread owns the element
+            c[(long)row * k2 + col] += wt.acc[mi][ni][r];
+          else
+            c[(long)row * k2 + col] = wt.acc[mi][ni][r];
         }
       }
 }
@@ -697,14 +699,31 @@ void launch_gemm_bf16_nn_a16(const void* a_v, const float* b, float* c, int m,
   }
 }
 
+// `acc` (here and in the two a16b16 launchers below): c and dbias are
+// gradient sinks that already hold a sum — no memset, the epilogue adds.
 void launch_gemm_bf16_tn_a16(const void* a_v, const float* b, float* c,
                              float* dbias, int m, int n, int k2,
-                             hipStream_t s) {
+                             hipStream_t s, bool acc) {
   const __bf16* a = (const __bf16*)a_v;
   const bool big = gemm_dispatch::tn_tile128(n, k2);
   const int tiles = gemm_dispatch::tn_tiles(n, k2);
   const int slices =
       gemm_dispatch::tn_slices(m, tiles, 64, pertgnn_deterministic());
+  if (acc) {
+    if (big)
+      gemm_bf16_tn_kernel<128, 128, 32, __bf16, __bf16, float, BGEMM_THREADS,
+                          true>
+          <<<dim3(tiles * slices), dim3(BGEMM_THREADS), 0, s>>>(a, b, c, dbias,
+                                                                m, n, k2,
+                                                                slices);
+    else
+      gemm_bf16_tn_kernel<64, 64, 64, __bf16, __bf16, float, BGEMM_THREADS,
+                          true>
+          <<<dim3(tiles * slices), dim3(BGEMM_THREADS), 0, s>>>(a, b, c, dbias,
+                                                                m, n, k2,
+                                                                slices);
+    return;
+  }
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
@@ -773,13 +792,32 @@ void launch_gemm_bf16_nn_a16o16(const void* a_v, const float* b, void* c_v,
 
 void launch_gemm_bf16_tn_a16b16(const void* a_v, const void* b_v, float* c,
                                 float* dbias, int m, int n, int k2,
-                                hipStream_t s) {
+                                hipStream_t s, bool acc) {
   const __bf16* a = (const __bf16*)a_v;
   const __bf16* b = (const __bf16*)b_v;
   const bool big = gemm_dispatch::tn_tile128(n, k2);
   const int tiles = gemm_dispatch::tn_tiles(n, k2);
   const int slices =
       gemm_dispatch::tn_slices(m, tiles, 64, pertgnn_deterministic());
+  if (acc) {
+    if (big && gemm_t512())
+      gemm_bf16_tn_kernel<128, 128, 32, __bf16, __bf16, __bf16, 512, true>
+          <<<dim3(tiles * slices), dim3(512), 0, s>>>(a, b, c, dbias, m, n,
+                                                      k2, slices);
+    else if (big)
+      gemm_bf16_tn_kernel<128, 128, 32, __bf16, __bf16, __bf16, BGEMM_THREADS,
+                          true>
+          <<<dim3(tiles * slices), dim3(BGEMM_THREADS), 0, s>>>(a, b, c, dbias,
+                                                                m, n, k2,
+                                                                slices);
+    else
+      gemm_bf16_tn_kernel<64, 64, 64, __bf16, __bf16, __bf16, BGEMM_THREADS,
+                          true>
+          <<<dim3(tiles * slices), dim3(BGEMM_THREADS), 0, s>>>(a, b, c, dbias,
+                                                                m, n, k2,
+                                                                slices);
+    return;
+  }
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
@@ -839,13 +877,28 @@ void launch_gemm_fp16_nn_a16o16(const void* a_v, const float* b, void* c_v,
 
 void launch_gemm_fp16_tn_a16b16(const void* a_v, const void* b_v, float* c,
                                 float* dbias, int m, int n, int k2,
-                                hipStream_t s) {
+                                hipStream_t s, bool acc) {
   const __bf16* a = (const __bf16*)a_v;
   const __bf16* b = (const __bf16*)b_v;
   const bool big = gemm_dispatch::tn_tile128(n, k2);
   const int tiles = gemm_dispatch::tn_tiles(n, k2);
   const int slices =
       gemm_dispatch::tn_slices(m, tiles, 64, pertgnn_deterministic());
+  if (acc) {
+    if (big)
+      gemm_bf16_tn_kernel<128, 128, 32, _Float16, __bf16, __bf16,
+                          BGEMM_THREADS, true>
+          <<<dim3(tiles * slices), dim3(BGEMM_THREADS), 0, s>>>(a, b, c, dbias,
+                                                                m, n, k2,
+                                                                slices);
+    else
+      gemm_bf16_tn_kernel<64, 64, 64, _Float16, __bf16, __bf16, BGEMM_THREADS,
+                          true>
+          <<<dim3(tiles * slices), dim3(BGEMM_THREADS), 0, s>>>(a, b, c, dbias,
+                                                                m, n, k2,
+                                                                slices);
+    return;
+  }
   if (slices > 1)
     HIP_CHECK(hipMemsetAsync(c, 0, (long)n * k2 * sizeof(float), s));
   if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
@@ -1223,7 +1276,7 @@ void launch_gemm_a16_glds_nt(const void* a_v, const void* b16_v,
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_g;
 
 template <int BM /*n cols*/, int BN /*k2 cols*/, int BKM /*m per step*/,
-          int THREADS = 512>
+          int THREADS = 512, bool ACC = false>
 __launch_bounds__(THREADS)
 __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
                                         const __bf16* __restrict__ b,
@@ -1405,20 +1458,24 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
       for (int r = 0; r < 4; ++r) {
         const int row = n0 + wm + mi * 16 + frow + r;
         const int col = k0 + wn + ni * 16 + fcol;
-        if (slices == 1)
-          c[(long)row * k2 + col] = acc[mi][ni][r];
-        else
+        if (slices != 1)
           atomicAdd(&c[(long)row * k2 + col], acc[mi][ni][r]);
+        else if (ACC)  // gradient sink: this thread owns the element
+          c[(long)row * k2 + col] += acc[mi][ni][r];
+        else
+          c[(long)row * k2 + col] = acc[mi][ni][r];
       }
 }
 
 // Both operands bf16 contract-major (g [m][n], x [m][k2]); the m tail rows
 // beyond the last BKM multiple are a partial last step inside the kernel.
 // When dbias sits right behind c (one [n*k2 + n] buffer, as the binding
-// allocates them) a single memset clears both.
+// allocates them) a single memset clears both.  `acc`: c and dbias are
+// gradient sinks that already hold a sum — nothing is cleared and every
+// element is added to.
 void launch_gemm_a16_glds_tn(const void* a_v, const void* b_v, float* c,
                              float* dbias, int m, int n, int k2,
-                             hipStream_t s) {
+                             hipStream_t s, bool acc) {
   const __bf16* a = (const __bf16*)a_v;
   const __bf16* b = (const __bf16*)b_v;
   constexpr int BM = 128, BN = 128, BKM = 64;
@@ -1427,6 +1484,12 @@ void launch_gemm_a16_glds_tn(const void* a_v, const void* b_v, float* c,
   // does not change the split (m and m - m % BKM slice alike)
   const int slices = gemm_dispatch::glds_tn_slices(m, tiles);
   const long nc = (long)n * k2;
+  if (acc) {
+    gemm_a16_glds_tn_kernel<BM, BN, BKM, 512, true>
+        <<<dim3(tiles * slices), dim3(512), 0, s>>>(a, b, c, dbias, m, n, k2,
+                                                    slices);
+    return;
+  }
   if (dbias == c + nc) {
     HIP_CHECK(hipMemsetAsync(c, 0, (nc + n) * sizeof(float), s));
   } else {
@@ -1567,7 +1630,10 @@ struct PTDgradArgs {
   int blk_beg[3];
   int h;
   int splits;   // >1: each block takes 1/splits of its table's pairs
-  int atomic;   // add into out (zeroed, or holding an earlier launch's sum)
+  // per table: 0 stores, 1 adds atomically (out is zeroed, a gradient sink
+  // shared by several blocks, or holds an earlier launch's sum), 2 adds with
+  // a plain read-modify-write (a gradient sink, one block per element)
+  int mode[2];
 };
 
 // dT_t (fp32) = sum_l dP_l (bf16) @ W_l (fp32) for both tables: the K loop
@@ -1608,8 +1674,9 @@ __global__ void ptables_dgrad_kernel(const PTDgradArgs p) {
   const int per = (npairs + p.splits - 1) / p.splits;
   const int l_beg = p.pair_beg[t] + min(npairs, split * per);
   const int l_end = p.pair_beg[t] + min(npairs, (split + 1) * per);
-  // an atomic block with no pairs adds nothing; a storing one writes zeros
-  if (p.atomic && l_beg >= l_end) return;
+  // an adding block with no pairs adds nothing; a storing one writes zeros
+  const int mode = p.mode[t];
+  if (mode != 0 && l_beg >= l_end) return;
 
   // Two-level sum: each pair's K = h chain runs in the MFMA accumulator from
   // zero, exactly as its per-layer dgrad would, and is then added to `tot`
@@ -1678,8 +1745,10 @@ __global__ void ptables_dgrad_kernel(const PTDgradArgs p) {
         const int row = m0 + wm + mi * 16 + frow + r;
         const int col = n0 + wn + ni * 16 + fcol;
         if (row < m && col < h) {
-          if (p.atomic)
+          if (mode == 1)
             atomicAdd(&c[(long)row * h + col], tot[mi][ni][r]);
+          else if (mode == 2)
+            c[(long)row * h + col] += tot[mi][ni][r];
           else
             c[(long)row * h + col] = tot[mi][ni][r];
         }
@@ -1694,6 +1763,7 @@ struct PTWgradArgs {
   int slices[PT_MAX_GROUPS];        // split-K over m_g; >1 adds atomically
   int blk_beg[PT_MAX_GROUPS + 1];
   int groups, h;
+  unsigned acc;  // bit g: dw[g] is a gradient sink, add instead of store
 };
 
 // dW_g (fp32) = dP_g^T (bf16) @ A_g (fp32), reducing over m_g
@@ -1725,7 +1795,8 @@ __global__ void ptables_wgrad_kernel(const PTWgradArgs p) {
   const int per_slice = ((m + slices - 1) / slices + BK - 1) / BK * BK;
   const int c_beg = slice * per_slice;
   const int c_end = min(m, c_beg + per_slice);
-  if (slices > 1 && c_beg >= c_end) return;
+  const bool acc = (p.acc >> g) & 1u;
+  if ((slices > 1 || acc) && c_beg >= c_end) return;
 
   BWaveTile<FM, FN, BK, __bf16> wt;
   wt.zero();
@@ -1760,10 +1831,12 @@ __global__ void ptables_wgrad_kernel(const PTWgradArgs p) {
         const int row = n0 + wm + mi * 16 + frow + r;
         const int col = k0 + wn + ni * 16 + fcol;
         if (row < h && col < h) {
-          if (slices == 1)
-            c[(long)row * h + col] = wt.acc[mi][ni][r];
-          else
+          if (slices != 1)
             atomicAdd(&c[(long)row * h + col], wt.acc[mi][ni][r]);
+          else if (acc)
+            c[(long)row * h + col] += wt.acc[mi][ni][r];
+          else
+            c[(long)row * h + col] = wt.acc[mi][ni][r];
         }
       }
 }
@@ -1799,15 +1872,18 @@ void launch_ptables_fwd(int groups, const float* const* a,
 }
 
 // table dgrad: npairs[t] (dP, W) pairs per table, table 0's first in dp/w.
-// Writes out[t] [m[t], h] unless `zeroed` (the caller cleared both outputs),
-// in which case every launch adds atomically and `splits` may exceed 1.
-// Without `zeroed` the sum order is fixed: launches past the first (more
-// pairs than one struct holds) add onto the stored result in stream order,
-// one block per element.
+// Writes out[t] [m[t], h] unless addto[t]: the caller cleared that output or
+// it is a gradient sink, and every launch adds to it.  `splits` may exceed 1
+// only when both outputs are added to (the adds are then atomic).  With
+// splits == 1 the sum order is fixed: one block per element, the first
+// launch stores (or, into a sink, adds with a plain read-modify-write) and
+// launches past the first (more pairs than one struct holds) add onto that
+// in stream order.
 void launch_ptables_dgrad(const void* const* dp, const float* const* w,
                           const int* npairs, float* const* out, const int* m,
-                          int h, int splits, bool zeroed, hipStream_t s) {
-  if (!zeroed) splits = 1;
+                          int h, int splits, const bool* addto,
+                          hipStream_t s) {
+  if (!(addto[0] && addto[1])) splits = 1;
   const int half = PT_MAX_GROUPS / 2;  // pairs per table per launch
   const int most = max(npairs[0], npairs[1]);
   bool first = true;
@@ -1827,13 +1903,14 @@ void launch_ptables_dgrad(const void* const* dp, const float* const* w,
       p.m[t] = m[t];
       p.blk_beg[t] = blocks;
       // a table with nothing (more) to add needs blocks only to store zeros
-      if (cnt > 0 || (first && !zeroed)) blocks += pt_tiles(m[t], h) * splits;
+      if (cnt > 0 || (first && !addto[t]))
+        blocks += pt_tiles(m[t], h) * splits;
+      p.mode[t] = (splits > 1 || !first) ? 1 : addto[t] ? 2 : 0;
     }
     p.pair_beg[2] = np;
     p.blk_beg[2] = blocks;
     p.h = h;
     p.splits = splits;
-    p.atomic = (zeroed || !first) ? 1 : 0;
     if (blocks > 0)
       ptables_dgrad_kernel<<<dim3(blocks), dim3(BGEMM_THREADS), 0, s>>>(p);
     first = false;
@@ -1842,11 +1919,14 @@ void launch_ptables_dgrad(const void* const* dp, const float* const* w,
 
 // weight wgrad: dw[g] [h,h] = dp[g]^T @ a[g] over m[g] rows.  Outside
 // PERTGNN_DETERMINISTIC=1 large-m groups are split-K'd with atomics, and the
-// caller must then have zeroed every dw (returns true if it relies on that);
-// `probe` only answers that question without launching.
+// caller must then have zeroed every dw that is not a gradient sink (returns
+// true if it relies on that); `probe` only answers that question without
+// launching.  sink[g] (may be null: none): dw[g] already holds a sum and is
+// added to, never stored or cleared.
 bool launch_ptables_wgrad(int groups, const void* const* dp,
                           const float* const* a, float* const* dw,
-                          const int* m, int h, bool probe, hipStream_t s) {
+                          const int* m, int h, bool probe, hipStream_t s,
+                          const bool* sink) {
   const bool det = pertgnn_deterministic();
   int total_tiles = 0;
   for (int g = 0; g < groups; ++g) total_tiles += pt_tiles(h, h);
@@ -1855,14 +1935,16 @@ bool launch_ptables_wgrad(int groups, const void* const* dp,
     PTWgradArgs p;
     p.groups = min(PT_MAX_GROUPS, groups - g0);
     p.h = h;
+    p.acc = 0u;
     int blocks = 0;
     for (int i = 0; i < p.groups; ++i) {
       const int mg = m[g0 + i];
+      if (sink && sink[g0 + i]) p.acc |= 1u << i;
       int slices = 1;
       while (!det && (long)total_tiles * slices < 2048 && slices < 64 &&
              (long)slices * 64 * 4 < mg)
         slices *= 2;
-      any_split |= slices > 1;
+      any_split |= slices > 1 && !(sink && sink[g0 + i]);
       p.dp[i] = (const __bf16*)dp[g0 + i];
       p.a[i] = a[g0 + i];
       p.dw[i] = dw[g0 + i];

@@ -1460,14 +1460,21 @@ __global__ void bn_bwd_apply_kernel(
   }
 }
 
-// dgamma[c] = sum gm*xhat = partials[h+c]; dbeta[c] = sum gm = partials[c]
+// dgamma[c] = sum gm*xhat = partials[h+c]; dbeta[c] = sum gm = partials[c];
+// acc: dgamma/dbeta are gradient sinks, added to instead of stored
 __global__ void bn_grad_affine_kernel(const float* __restrict__ partials,
                                       float* __restrict__ dgamma,
-                                      float* __restrict__ dbeta, int h) {
+                                      float* __restrict__ dbeta, int h,
+                                      int acc) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= h) return;
-  dgamma[c] = partials[h + c];
-  dbeta[c] = partials[c];
+  if (acc) {
+    dgamma[c] += partials[h + c];
+    dbeta[c] += partials[c];
+  } else {
+    dgamma[c] = partials[h + c];
+    dbeta[c] = partials[c];
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -1701,7 +1708,8 @@ __device__ __forceinline__ void bn_finalize_one(
 
 // fixed-order fold of the slab rows of a wide reduction into partials[2h],
 // with the per-channel epilogue of its direction fused in (no extra launch,
-// no memset): EPI 1 = bn_finalize math, EPI 2 = dgamma/dbeta copy.
+// no memset): EPI 1 = bn_finalize math, EPI 2 = dgamma/dbeta copy, EPI 3 =
+// dgamma/dbeta added into gradient sinks.
 // Block = 8 channels x {sum, sumsq} x 16 row slices; slices are folded in
 // slice order, rows inside a slice in row order.
 template <int EPI>
@@ -1739,9 +1747,12 @@ __global__ __launch_bounds__(256) void bn_slab_fold_kernel(
     if (EPI == 1) {
       bn_finalize_one(ch, tot[threadIdx.x], tot[8 + threadIdx.x], (float)n,
                       eps, momentum, o0, o1, running_mean, running_var);
-    } else {
+    } else if (EPI == 2) {
       o0[ch] = tot[8 + threadIdx.x];  // dgamma = sum gm*xhat
       o1[ch] = tot[threadIdx.x];      // dbeta = sum gm
+    } else {
+      o0[ch] += tot[8 + threadIdx.x];
+      o1[ch] += tot[threadIdx.x];
     }
   }
 }
@@ -1778,13 +1789,14 @@ static void bn_stats_wide_launch(const TS* x, long n, int h,
 }
 
 // wide backward partials into partials[2h]; dgamma != nullptr also writes
-// dgamma/dbeta.  mask (uint8 [n, h/8]) takes precedence over y.
+// dgamma/dbeta (acc: adds them into gradient sinks).  mask (uint8 [n, h/8])
+// takes precedence over y.
 template <typename TS>
 static void bn_bwd_partials_wide_launch(
     const TS* g, const TS* x, const TS* y,
     const unsigned char* mask, const float* mean, const float* invstd, long n,
     int h, bool relu, float* partials, float* slab, float* dgamma,
-    float* dbeta, float keep_inv, hipStream_t s) {
+    float* dbeta, float keep_inv, hipStream_t s, bool acc = false) {
   const int nb = bn_wide_blocks(n);
   float* out = slab ? slab : partials;
   const int sl = slab ? 1 : 0;
@@ -1800,7 +1812,11 @@ static void bn_bwd_partials_wide_launch(
     bn_bwd_partial_wide_kernel<TS, 1, U><<<nb, 256, 0, s>>>(
         g, x, y, mean, invstd, n, h, out, sl, keep_inv);
   if (slab) {
-    if (dgamma)
+    if (dgamma && acc)
+      bn_slab_fold_kernel<3><<<h / 8, 256, 0, s>>>(
+          slab, nb, h, partials, n, 0.f, 0.f, dgamma, dbeta, nullptr,
+          nullptr);
+    else if (dgamma)
       bn_slab_fold_kernel<2><<<h / 8, 256, 0, s>>>(
           slab, nb, h, partials, n, 0.f, 0.f, dgamma, dbeta, nullptr,
           nullptr);
@@ -1809,8 +1825,8 @@ static void bn_bwd_partials_wide_launch(
           slab, nb, h, partials, n, 0.f, 0.f, nullptr, nullptr, nullptr,
           nullptr);
   } else if (dgamma) {
-    bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(partials, dgamma,
-                                                           dbeta, h);
+    bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+        partials, dgamma, dbeta, h, acc ? 1 : 0);
   }
 }
 
@@ -2024,9 +2040,9 @@ void launch_bn_bwd_apply_only(const float* g, const float* x, const float* y,
 }
 
 void launch_bn_grad_affine(const float* partials, float* dgamma, float* dbeta,
-                           int h, hipStream_t s) {
-  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(partials, dgamma,
-                                                         dbeta, h);
+                           int h, hipStream_t s, bool acc) {
+  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+      partials, dgamma, dbeta, h, acc ? 1 : 0);
 }
 
 void launch_bn_fwd(const float* x, const float* gamma, const float* beta,
@@ -2065,12 +2081,13 @@ void launch_bn_bwd(const float* g, const float* x, const float* y,
                    const float* mean, const float* invstd, const float* gamma,
                    float* partials, float* dx, float* dgamma, float* dbeta,
                    long n, int h, bool relu, float keep_inv, float* slab,
-                   hipStream_t s) {
+                   hipStream_t s, bool acc) {
   if (n == 0) return;
   const bool wide = bn_wide_ok(h);
   if (wide)
     bn_bwd_partials_wide_launch(g, x, y, nullptr, mean, invstd, n, h, relu,
-                                partials, slab, dgamma, dbeta, keep_inv, s);
+                                partials, slab, dgamma, dbeta, keep_inv, s,
+                                acc);
   else
     bn_bwd_partials_dispatch(g, x, y, mean, invstd, n, h, relu, partials,
                              keep_inv, s);
@@ -2078,8 +2095,8 @@ void launch_bn_bwd(const float* g, const float* x, const float* y,
       g, x, y, mean, invstd, gamma, partials, dx, n, n, h, relu ? 1 : 0,
       nullptr, keep_inv);
   if (wide) return;  // dgamma/dbeta written with the partials
-  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(partials, dgamma,
-                                                         dbeta, h);
+  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+      partials, dgamma, dbeta, h, acc ? 1 : 0);
 }
 
 // --- act16 launchers: fully bf16 activation streams — x (the conv output /
@@ -2198,13 +2215,13 @@ void launch_bn_bwd_partials_affine16(const void* g, const void* x,
                                      long n, int h, float* partials,
                                      float keep_inv, float* slab,
                                      float* dgamma, float* dbeta,
-                                     hipStream_t s) {
+                                     hipStream_t s, bool acc) {
   if (n <= 0 || !mask || !bn_wide_ok(h))
     pertgnn_shape_fail("bn_bwd_partials_affine16", "h", h);
   bn_bwd_partials_wide_launch((const __bf16*)g, (const __bf16*)x,
                               (const __bf16*)nullptr, mask, mean, invstd, n,
                               h, true, partials, slab, dgamma, dbeta,
-                              keep_inv, s);
+                              keep_inv, s, acc);
 }
 
 void launch_bn_bwd_apply_only16(const void* g, const void* x, const void* y,
@@ -2236,14 +2253,14 @@ void launch_bn_bwd16(const void* g, const void* x, const void* y,
                      const float* gamma, float* partials, void* dx,
                      float* dgamma, float* dbeta, long n, int h, bool relu,
                      float keep_inv, float* slab, const unsigned char* mask,
-                     hipStream_t s) {
+                     hipStream_t s, bool acc) {
   if (n == 0) return;
   const bool wide = bn_wide_ok(h);
   if (wide)
     bn_bwd_partials_wide_launch((const __bf16*)g, (const __bf16*)x,
                                 (const __bf16*)y, mask, mean, invstd, n, h,
                                 relu, partials, slab, dgamma, dbeta, keep_inv,
-                                s);
+                                s, acc);
   else
     bn_bwd_partials_dispatch((const __bf16*)g, (const __bf16*)x,
                              (const __bf16*)y, mean, invstd, n, h, relu,
@@ -2262,8 +2279,8 @@ void launch_bn_bwd16(const void* g, const void* x, const void* y,
         gamma, partials, (__bf16*)dx, n, n, h, relu ? 1 : 0, nullptr,
         keep_inv);
   if (wide) return;  // dgamma/dbeta written with the partials
-  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(partials, dgamma,
-                                                         dbeta, h);
+  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+      partials, dgamma, dbeta, h, acc ? 1 : 0);
 }
 
 // ---------------------------------------------------------------------------

@@ -31,6 +31,61 @@ def deterministic() -> bool:
     return os.environ.get("PERTGNN_DETERMINISTIC", "0") == "1"
 
 
+def grad_sink(p):
+    """The gradient sink of parameter ``p`` for the forward being recorded,
+    or None.  The sink is the slice of FusedAdam's ``flat_grad`` that
+    ``p.grad`` is pinned to; a backward op given one adds the parameter's
+    gradient straight into it and returns None for ``p``, so autograd's
+    AccumulateGrad (one small add launch per parameter) never runs and the
+    op clears no buffer of its own.  The wrappers hand such a parameter to
+    their autograd node detached (``_sunk``), so no AccumulateGrad node and
+    none of its hooks exist for that use.  Used only while all of these hold:
+    grad mode is on and ``p`` requires grad; ``p.grad`` still aliases the
+    sink (``zero_grad(set_to_none=True)`` or a re-pointed ``.grad`` restore
+    the return path until the optimizer's ``zero_grad`` re-pins); no live
+    FlatGradAllReduce (enabled, distributed) waits for ``p``'s
+    post-accumulate hook, which needs autograd to see the parameter;
+    PERTGNN_NO_GRAD_SINK is not 1 (read per call, so one process can run
+    both paths)."""
+    sink = getattr(p, "_grad_sink", None)
+    if sink is None or not p.requires_grad or not torch.is_grad_enabled():
+        return None
+    import os
+    if os.environ.get("PERTGNN_NO_GRAD_SINK", "0") == "1":
+        return None
+    g = p.grad
+    if g is None or g.data_ptr() != sink.data_ptr() or g.shape != sink.shape:
+        return None
+    engine = getattr(p, "_grad_sink_engine", None)
+    if engine is not None and engine.enabled and engine.comm.distributed:
+        return None
+    return sink
+
+
+def _sunk(p, sink):
+    """``p`` as its autograd node takes it: detached when its gradient goes
+    to ``sink`` (the node returns None for it either way, but a detached
+    input has no AccumulateGrad node whose hooks would still run)."""
+    return p if sink is None or p is None else p.detach()
+
+
+_SINK_ANCHOR: dict = {}
+
+
+def _sink_anchor(device):
+    """An empty leaf that requires grad, passed to every node that may take
+    its parameters detached: with no other input requiring grad (the first
+    layer's linear16 reads the input features) the node would otherwise
+    drop out of the graph and its backward, which fills the sinks, would
+    never run.  Its own gradient is always None."""
+    key = str(device)
+    a = _SINK_ANCHOR.get(key)
+    if a is None:
+        a = torch.empty(0, device=device, requires_grad=True)
+        _SINK_ANCHOR[key] = a
+    return a
+
+
 def _table_grad(m, g, idx, rows, h, col_off):
     """dtable[v] = segment-sum of g[:, col_off:col_off+h] by idx — LDS vocab
     accumulator for small tables, work-balanced deterministic grouped
@@ -396,10 +451,12 @@ class _Linear16Fn(torch.autograd.Function):
     matrix cores, so numerics match the plain bf16-GEMM mode)."""
 
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, w_sink=None, b_sink=None, anchor=None):
         m = ext()
         bb = b if b is not None else torch.empty(0, dtype=torch.float32, device=x.device)
         fp16c = gemm_precision() == "fp16"  # fp16 matrix cores, bf16 IO
+        # gradient sinks of w and b (grad_sink): the wgrad adds into them
+        ctx.w_sink, ctx.b_sink = w_sink, b_sink
         # the forward's weight-convert launch also writes the transposed bf16
         # image the dgrad needs (w cannot change in between: it stays a saved
         # tensor, so autograd's version check catches an in-place update)
@@ -424,15 +481,27 @@ class _Linear16Fn(torch.autograd.Function):
         g = g.contiguous()
         if x.dtype == torch.bfloat16:
             dx = m.linear_dgrad16_o16(g, w, ctx.fp16c, ctx.wt16)
-            dw, db = m.linear_wgrad16_b16(g, x, ctx.has_bias, ctx.fp16c)
+            dw, db = m.linear_wgrad16_b16(g, x, ctx.has_bias, ctx.fp16c,
+                                          ctx.w_sink, ctx.b_sink)
         else:
             dx = m.linear_dgrad16(g, w)
-            dw, db = m.linear_wgrad16(g, x, ctx.has_bias)
-        return dx, dw, (db if ctx.has_bias else None)
+            dw, db = m.linear_wgrad16(g, x, ctx.has_bias, ctx.w_sink,
+                                      ctx.b_sink)
+        if ctx.w_sink is not None:  # dw and db are in the sinks
+            return dx, None, None, None, None, None
+        return dx, dw, (db if ctx.has_bias else None), None, None, None
 
 
 def linear16(x, w, b=None):
-    return _Linear16Fn.apply(x, w, b)
+    # w and b sink together or not at all: one launcher flag covers both
+    w_sink = grad_sink(w)
+    b_sink = grad_sink(b) if b is not None else None
+    if w_sink is None or (b is not None and b_sink is None):
+        w_sink = b_sink = None
+    if w_sink is None:
+        return _Linear16Fn.apply(x, w, b)
+    return _Linear16Fn.apply(x, _sunk(w, w_sink), _sunk(b, b_sink), w_sink,
+                             b_sink, _sink_anchor(x.device))
 
 
 class _PTablesFn(torch.autograd.Function):
@@ -443,9 +512,12 @@ class _PTablesFn(torch.autograd.Function):
     table gradients and one wgrad launch fills all 2L weight gradients."""
 
     @staticmethod
-    def forward(ctx, ifc_table, rpc_table, *weights):
+    def forward(ctx, sinks, anchor, ifc_table, rpc_table, *weights):
         layers = len(weights) // 2
         we_ifc, we_rpc = list(weights[:layers]), list(weights[layers:])
+        # gradient sinks (grad_sink) of the two tables and the 2L weights,
+        # None where an input has none
+        ctx.sinks = sinks
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(ifc_table, rpc_table, *weights)
         return tuple(ext().ptables_fwd(ifc_table, rpc_table, we_ifc, we_rpc))
@@ -455,12 +527,19 @@ class _PTablesFn(torch.autograd.Function):
         ifc_table, rpc_table, *weights = ctx.saved_tensors
         layers = len(weights) // 2
         none = torch.empty(0, dtype=torch.bfloat16, device=ifc_table.device)
+        t_sinks, w_sinks = ctx.sinks[:2], list(ctx.sinks[2:])
         d_ifc, d_rpc, dw = ext().ptables_bwd(
             [none if g is None else g.contiguous() for g in dps],
             ifc_table, rpc_table, weights[:layers], weights[layers:],
-            ptable_dgrad_splits())
-        return (d_ifc, d_rpc,
-                *(None if g is None else dw[i] for i, g in enumerate(dps)))
+            ptable_dgrad_splits(), t_sinks[0], t_sinks[1], w_sinks)
+        # dw holds the groups without a sink, in order
+        slot, dws = 0, []
+        for g, sink in zip(dps, w_sinks):
+            dws.append(None if g is None or sink is not None else dw[slot])
+            slot += sink is None
+        return (None, None,
+                None if t_sinks[0] is not None else d_ifc,
+                None if t_sinks[1] is not None else d_rpc, *dws)
 
 
 def ptables_grouped(ifc_table, rpc_table, we_ifc, we_rpc):
@@ -469,7 +548,10 @@ def ptables_grouped(ifc_table, rpc_table, we_ifc, we_rpc):
     if len(we_ifc) != len(we_rpc):
         raise ValueError(f"{len(we_ifc)} we_ifc vs {len(we_rpc)} we_rpc")
     layers = len(we_ifc)
-    out = _PTablesFn.apply(ifc_table, rpc_table, *we_ifc, *we_rpc)
+    params = (ifc_table, rpc_table, *we_ifc, *we_rpc)
+    sinks = tuple(grad_sink(p) for p in params)
+    out = _PTablesFn.apply(sinks, _sink_anchor(ifc_table.device),
+                           *(_sunk(p, s) for p, s in zip(params, sinks)))
     return list(out[:layers]), list(out[layers:])
 
 
@@ -825,10 +907,12 @@ def _bn_forward(m, x, gamma, beta, running_mean, running_var, momentum, eps,
 class _BNReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps,
-                training, fuse_relu, comm, out16=False, dropout_p=0.0):
+                training, fuse_relu, comm, out16=False, dropout_p=0.0,
+                sinks=(None, None), anchor=None):
         y, save_mean, save_invstd, mask, sync, keep_inv = _bn_forward(
             ext(), x, gamma, beta, running_mean, running_var, momentum, eps,
             training, fuse_relu, comm, dropout_p)
+        ctx.sinks = sinks  # gradient sinks of gamma and beta, both or neither
         ctx.save_for_backward(x, gamma, save_mean, save_invstd,
                               y if mask is None else mask)
         ctx.y16 = y.dtype == torch.bfloat16
@@ -854,15 +938,24 @@ class _BNReLUFn(torch.autograd.Function):
             ctx.comm.all_reduce_(partials_global)
             dx, dgamma, dbeta = bwd_apply(
                 g, x, y, save_mean, save_invstd, gamma,
-                partials_global, partials_local, ctx.fuse_relu, ctx.keep_inv)
+                partials_global, partials_local, ctx.fuse_relu, ctx.keep_inv,
+                *ctx.sinks)
         else:
             bwd = m.bn_relu_bwd16 if y16 else m.bn_relu_bwd
             dx, dgamma, dbeta = bwd(
                 g, x, gamma, save_mean, save_invstd, y, ctx.fuse_relu,
-                ctx.keep_inv
+                ctx.keep_inv, *ctx.sinks
             )
-        return (dx, dgamma, dbeta, None, None, None, None, None, None, None,
-                None, None)
+        if ctx.sinks[0] is not None:  # dgamma and dbeta are in the sinks
+            dgamma = dbeta = None
+        return (dx, dgamma, dbeta) + (None,) * 11
+
+
+def _bn_sinks(gamma, beta):
+    """(dgamma sink, dbeta sink) as the BN backward ops take them: both or
+    (None, None)."""
+    sinks = (grad_sink(gamma), grad_sink(beta))
+    return sinks if None not in sinks else (None, None)
 
 
 def bn_attn_fuse_enabled(h: int) -> bool:
@@ -885,8 +978,10 @@ class _AttnBNReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkvs, pifc, prpc, gamma, beta, edge_attr, row_ptr,
                 csr_src, col_ptr, csc_dst, csc_eid, heads, running_mean,
-                running_var, momentum, eps, comm, dropout_p):
+                running_var, momentum, eps, comm, dropout_p,
+                sinks=(None, None), anchor=None):
         m = ext()
+        ctx.sinks = sinks  # gradient sinks of gamma and beta, both or neither
         x, alpha = m.edge_attn_fused_fwd(qkvs, pifc, prpc, edge_attr, row_ptr,
                                          csr_src, True, heads)
         y, save_mean, save_invstd, mask, sync, keep_inv = _bn_forward(
@@ -910,7 +1005,7 @@ class _AttnBNReLUFn(torch.autograd.Function):
          csc_dst, csc_eid, x, save_mean, save_invstd, mask) = ctx.saved_tensors
         m = ext()
         g = g.contiguous()
-        partials = ()
+        partials = (None, None)
         if ctx.comm is not None:
             # as _BNReLUFn.backward: local [2h+1] partials, one all-reduce
             # for the global sums and count
@@ -922,9 +1017,11 @@ class _AttnBNReLUFn(torch.autograd.Function):
         dqkvs, de, dgamma, dbeta = m.edge_attn_bn_bwd16(
             g, x, mask, gamma, save_mean, save_invstd, ctx.keep_inv, qkvs,
             pifc, prpc, edge_attr, alpha, row_ptr, csr_src, col_ptr, csc_dst,
-            csc_eid, ctx.heads, *partials)
+            csc_eid, ctx.heads, *partials, *ctx.sinks)
         dpifc, dprpc = _attn_table_grads(m, de, pifc, prpc, edge_attr)
-        return (dqkvs, dpifc, dprpc, dgamma, dbeta) + (None,) * 13
+        if ctx.sinks[0] is not None:  # dgamma and dbeta are in the sinks
+            dgamma = dbeta = None
+        return (dqkvs, dpifc, dprpc, dgamma, dbeta) + (None,) * 15
 
 
 def edge_attention_fused_bn_relu(qkvs, pifc, prpc, edge_attr, csr, gamma,
@@ -935,10 +1032,12 @@ def edge_attention_fused_bn_relu(qkvs, pifc, prpc, edge_attr, csr, gamma,
     GPU, ``bn_attn_fuse_enabled(h)``): same forward ops, same results, one
     pass over [N, H] less in the backward."""
     row_ptr, csr_src, col_ptr, csc_dst, csc_eid = csr
+    sinks = _bn_sinks(gamma, beta)
     return _AttnBNReLUFn.apply(
-        qkvs, pifc, prpc, gamma, beta, edge_attr, row_ptr, csr_src, col_ptr,
-        csc_dst, csc_eid, heads, running_mean, running_var, momentum, eps,
-        comm, dropout_p)
+        qkvs, pifc, prpc, _sunk(gamma, sinks[0]), _sunk(beta, sinks[1]),
+        edge_attr, row_ptr, csr_src, col_ptr, csc_dst, csc_eid, heads,
+        running_mean, running_var, momentum, eps, comm, dropout_p, sinks,
+        _sink_anchor(qkvs.device))
 
 
 class _EagerSyncBNFn(torch.autograd.Function):
@@ -1009,9 +1108,12 @@ def batchnorm_relu(x, gamma, beta, running_mean, running_var, momentum, eps,
     stays fp32, only the activation stream narrows — the downstream QKVS
     GEMM and its wgrad then read half the bytes."""
     if use_hip(x):
-        return _BNReLUFn.apply(x, gamma, beta, running_mean, running_var,
-                               momentum, eps, training, fuse_relu, comm,
-                               out16, dropout_p)
+        sinks = _bn_sinks(gamma, beta)
+        return _BNReLUFn.apply(x, _sunk(gamma, sinks[0]),
+                               _sunk(beta, sinks[1]), running_mean,
+                               running_var, momentum, eps, training,
+                               fuse_relu, comm, out16, dropout_p, sinks,
+                               _sink_anchor(x.device))
     if comm is not None and getattr(comm, "distributed", False) and training:
         y = _eager_sync_batchnorm(x, gamma, beta, running_mean, running_var,
                                   momentum, eps, fuse_relu, comm)

@@ -73,6 +73,11 @@ class GradBucketAllReduce:
 
         for p in self.params:
             p.register_post_accumulate_grad_hook(self._hook)
+            # keeps FusedAdam's gradient sinks off (ops.functional.grad_sink):
+            # a sunk parameter is invisible to autograd and to these hooks
+            p._grad_sink_engine = self
+
+    enabled = True  # read by grad_sink, as FlatGradAllReduce.enabled
 
     def _seal(self, params, device):
         b = Bucket(list(params), device)

@@ -68,15 +68,24 @@ class FusedAdam:
             self.offsets.append(off)
             self.flat_param[off:off + n].copy_(p.data.reshape(-1))
             p.data = self.flat_param[off:off + n].view_as(p.data)
-            p.grad = self.flat_grad[off:off + n].view_as(p.data)
+            self._pin_grad(p, off)
             off += n
+
+    def _pin_grad(self, p, off):
+        """Point ``p.grad`` at its ``flat_grad`` slice and record that slice
+        as the parameter's gradient sink: the native backward ops add a
+        parameter's gradient straight into it (ops.functional.grad_sink)
+        for as long as ``p.grad`` still aliases it."""
+        view = self.flat_grad[off:off + p.numel()].view_as(p.data)
+        p.grad = view
+        p._grad_sink = view
 
     def zero_grad(self, set_to_none: bool = False):
         self.flat_grad.zero_()
         # autograd may have replaced p.grad (e.g. set_to_none elsewhere) — re-pin
         for p, off in zip(self.params, self.offsets):
             if p.grad is None or p.grad.data_ptr() != self.flat_grad[off:off + p.numel()].data_ptr():
-                p.grad = self.flat_grad[off:off + p.numel()].view_as(p.data)
+                self._pin_grad(p, off)
 
     def scale_loss(self, loss):
         """Multiply the loss by the active scale before backward: the
@@ -202,6 +211,11 @@ class FlatGradAllReduce:
                 self.param2bucket[id(p)] = b
         for p in self.opt.params:
             p.register_post_accumulate_grad_hook(self._hook)
+            # a sunk parameter enters its autograd node detached, so its hooks
+            # would never fire: while this engine is live (enabled,
+            # distributed) the ops keep returning gradients instead of adding
+            # into the sinks (ops.functional.grad_sink reads this)
+            p._grad_sink_engine = self
 
     def _seal(self, lo, hi, params):
         self.buckets.append({"lo": lo, "hi": hi, "params": list(params),
