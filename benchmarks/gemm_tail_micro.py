@@ -1,7 +1,10 @@
 """The act16 dgrad and wgrad ops at the flagship shape with and without an m
 tail, each call repeated between device events (profiles/18).
 
-    python benchmarks/gemm_tail_micro.py [TAG]
+    python benchmarks/gemm_tail_micro.py [TAG] [TILE]
+
+TILE forces the wgrad's output tile (1 / 2 / 3 = 128x128 / 256x128 / 256x256;
+default 0, the dispatch's choice; profiles/21).
 
 m = 1412 * 128 is tail-free for every tile; m + 26 leaves 26 rows past the
 last 128-row (and 64-row) tile.  The dgrad figure includes the transposed
@@ -37,6 +40,7 @@ def timeit(f, iters=200, warm=30):
 
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "tree"
+    tile = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(5)
     w = (torch.randn(N, K, generator=g) * 0.05).to(dev)
@@ -46,7 +50,7 @@ def main():
         for m in (M_FULL, M_TAIL):
             gy, x = gy_all[:m], x_all[:m]
             t_d = timeit(lambda: C.linear_dgrad16_o16(gy, w))
-            t_w = timeit(lambda: C.linear_wgrad16_b16(gy, x, True))
+            t_w = timeit(lambda: C.linear_wgrad16_b16(gy, x, True, tile=tile))
             print(f"{tag} rep{rep} m={m}: dgrad op {t_d:.2f} us  "
                   f"wgrad op {t_w:.2f} us", flush=True)
 

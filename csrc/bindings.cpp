@@ -261,7 +261,13 @@ void launch_convert_w16(const float*, void*, long, hipStream_t);
 void launch_convert_w16_both(const float*, void*, void*, int, int,
                              hipStream_t);
 void launch_gemm_a16_glds_tn(const void*, const void*, float*, float*, int,
-                             int, int, hipStream_t, bool acc = false);
+                             int, int, hipStream_t, bool acc = false,
+                             int tile = 0);
+// the tile (gemm_dispatch::TnTile) that launcher runs for a shape it
+// supports: `tile` if forced (-1 where the shape does not allow it), else
+// the process-wide override or the dispatch's choice
+int glds_tn_tile_for(int m, int n, int k2, int tile);
+void set_glds_tn_tile(int tile);
 void launch_transpose_convert_w16(const float*, void*, int, int, hipStream_t);
 void launch_gemm_skinny_nn(const void*, const float*, float*, int, int, int,
                            hipStream_t);
@@ -1248,8 +1254,13 @@ torch::Tensor linear_dgrad16(torch::Tensor g, torch::Tensor w) {
 std::vector<torch::Tensor> linear_wgrad16(torch::Tensor g, torch::Tensor x,
                                           bool has_bias,
                                           OptTensor dw_sink = std::nullopt,
-                                          OptTensor db_sink = std::nullopt) {
+                                          OptTensor db_sink = std::nullopt,
+                                          int64_t tile = 0) {
   CHECK_IN(g); CHECK_IN(x);
+  // `tile` as in linear_wgrad16_b16; with fp32 x no shape reaches the glds
+  // TN kernel, so none can be forced
+  TORCH_CHECK(tile == 0, "linear_wgrad16: fp32 x does not run on the glds TN "
+                         "kernel, no tile to force");
   const int m = x.size(0);
   const int k = x.size(1);
   const int n = g.size(1);
@@ -1670,11 +1681,21 @@ std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
                                               bool has_bias,
                                               bool fp16c = false,
                                               OptTensor dw_sink = std::nullopt,
-                                              OptTensor db_sink = std::nullopt) {
+                                              OptTensor db_sink = std::nullopt,
+                                              int64_t tile = 0) {
   CHECK_IN(g); CHECK_IN(x);
   const int m = x.size(0);
   const int k = x.size(1);
   const int n = g.size(1);
+  // tile != 0 forces an output tile of the glds TN kernel (1 / 2 / 3 =
+  // 128x128 / 256x128 / 256x256) for any shape that kernel supports
+  const char* det = getenv("PERTGNN_DETERMINISTIC");
+  const bool glds = gemm_dispatch::wgrad_glds_ok(m, n, k, det && det[0] == '1');
+  TORCH_CHECK(tile == 0 ||
+                  (glds && !fp16c && glds_tn_tile_for(m, n, k, (int)tile) > 0),
+              "linear_wgrad16_b16: tile ", tile, " cannot run [", m, ", ", n,
+              "]^T x [", m, ", ", k, "] (needs bf16 compute, m >= 512, n "
+              "and k multiples of the tile, not deterministic)");
   auto fopt = x.options().dtype(torch::kFloat32);
   float* dw_ptr = grad_sink(dw_sink, x, {n, k}, "linear_wgrad16_b16");
   float* db_ptr = grad_sink(db_sink, x, {n}, "linear_wgrad16_b16");
@@ -1705,10 +1726,9 @@ std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
   }
   // glds TN fast path (panel-major images + ds_read_b64_tr_b16 fragments);
   // split-K atomics => not for the deterministic mode
-  const char* det = getenv("PERTGNN_DETERMINISTIC");
-  if (gemm_dispatch::wgrad_glds_ok(m, n, k, det && det[0] == '1')) {
+  if (glds) {
     launch_gemm_a16_glds_tn(g.data_ptr(), x.data_ptr(), dw_ptr, db_ptr, m, n,
-                            k, cur_stream(), acc);
+                            k, cur_stream(), acc, (int)tile);
     return {dw, db};
   }
   launch_gemm_bf16_tn_a16b16(g.data_ptr(), x.data_ptr(), dw_ptr, db_ptr, m, n,
@@ -1766,10 +1786,32 @@ std::string linear_path(const std::string& op, int64_t m64, int64_t n64,
   }
   if (a16 && prec == 1 && gd::wgrad_glds_ok(m, n, k, deterministic))
     return "glds_tn/s=" +
-           std::to_string(gd::glds_tn_slices(m, (n / 128) * (k / 128)));
+           std::to_string(gd::glds_tn_slices(
+               m, gd::glds_tn_tiles(gd::glds_tn_tile(m, n, k), n, k)));
   return fam + "_tn_" + tile(gd::tn_tile128(n, k)) + fp16 + "/s=" +
          std::to_string(gd::tn_slices(m, gd::tn_tiles(n, k),
                                       prec == 0 ? 32 : 64, deterministic));
+}
+
+// Output tile of the glds TN wgrad (linear_wgrad16_b16, bf16 compute) at a
+// shape, as it runs in this process: "128x128", "256x128" or "256x256";
+// "none" where the shape is not on that kernel.  Unlike linear_path it
+// follows set_wgrad_tile.
+std::string wgrad_tile(int64_t m, int64_t n, int64_t k, bool deterministic) {
+  TORCH_CHECK(m >= 0 && n > 0 && k > 0 && m <= INT_MAX && n <= INT_MAX &&
+                  k <= INT_MAX, "wgrad_tile: bad shape");
+  if (!gemm_dispatch::wgrad_glds_ok((int)m, (int)n, (int)k, deterministic))
+    return "none";
+  return gemm_dispatch::tn_tile_name(
+      glds_tn_tile_for((int)m, (int)n, (int)k, gemm_dispatch::TN_AUTO));
+}
+
+// Test hook: the tile every later glds TN wgrad of this process takes where
+// its shape allows it (0: back to the dispatch's choice).
+void set_wgrad_tile(int64_t tile) {
+  TORCH_CHECK(tile >= 0 && tile <= gemm_dispatch::TN_256x256,
+              "set_wgrad_tile: tile must be 0 (auto), 1, 2 or 3");
+  set_glds_tn_tile((int)tile);
 }
 
 // Every label linear_path can return, as "io|prec|op|label"; the wgrad labels
@@ -2015,7 +2057,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("linear_dgrad16", &linear_dgrad16);
   mod.def("linear_wgrad16", &linear_wgrad16, py::arg("g"), py::arg("x"),
           py::arg("has_bias"), py::arg("dw_sink") = py::none(),
-          py::arg("db_sink") = py::none());
+          py::arg("db_sink") = py::none(), py::arg("tile") = 0);
   mod.def("vocab_scatter_dual", &vocab_scatter_dual);
   mod.def("linear_dgrad", &linear_dgrad);
   mod.def("linear_wgrad", &linear_wgrad);
@@ -2122,7 +2164,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("wt16") = py::none());
   mod.def("linear_wgrad16_b16", &linear_wgrad16_b16, py::arg("g"),
           py::arg("x"), py::arg("has_bias"), py::arg("fp16c") = false,
-          py::arg("dw_sink") = py::none(), py::arg("db_sink") = py::none());
+          py::arg("dw_sink") = py::none(), py::arg("db_sink") = py::none(),
+          py::arg("tile") = 0);
+  mod.def("wgrad_tile", &wgrad_tile, py::arg("m"), py::arg("n"), py::arg("k"),
+          py::arg("deterministic") = false);
+  mod.def("set_wgrad_tile", &set_wgrad_tile, py::arg("tile"));
   mod.def("linear_path", &linear_path, py::arg("op"), py::arg("m"),
           py::arg("n"), py::arg("k"), py::arg("io"), py::arg("prec"),
           py::arg("deterministic") = false);

@@ -1265,11 +1265,13 @@ void launch_gemm_a16_glds_nt(const void* a_v, const void* b16_v,
 // glds TN kernel (wgrad): dw[n,k2] = sum_m g[m,n]^T x[m,k2].  Both operands
 // are contract(m)-major in HBM, so the NT kernel's row-linear glds image
 // cannot feed k-minor MFMA fragments.  Instead each operand tile is staged
-// as PANEL-MAJOR images — 16-column panels of [BKM m][16 cols] row-major
-// (the per-lane glds source addresses assemble them directly) — and the
-// MFMA fragments are read with gfx950's ds_read_b64_tr_b16 hardware
-// transpose-read (lane gets 4 contract-consecutive elements at 32-B
-// stride; two reads make the 8-element k fragment).  Split-K over m with
+// as an image of 256-B blocks, [8 m][16 cols] row-major, ordered
+// [64-column group][m octet][4 panels of 16 columns] (the per-lane glds
+// source addresses assemble them directly; one wave-instruction fetches 8
+// rows x 128 B, whole lines) — and the MFMA fragments are read with
+// gfx950's ds_read_b64_tr_b16 hardware transpose-read (lane gets 4
+// contract-consecutive elements at 32-B stride; two reads, the halves of
+// one block, make the 8-element k fragment).  Split-K over m with
 // atomicAdd combine, same contract as the register-staging TN kernel.
 // ---------------------------------------------------------------------------
 
@@ -1286,11 +1288,15 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
   constexpr int NWAVE = THREADS / PERTGNN_WAVE;
   constexpr int WCOL = NWAVE / 2;
   constexpr int FM = (BM / 2) / 16, FN = (BN / WCOL) / 16;
-  constexpr int PANEL_BYTES = BKM * 32;            // [BKM][16] bf16
+  constexpr int OCTS = BKM / 8;                    // m octets per step
+  constexpr int GROUP_BYTES = OCTS * 1024;         // [OCTS][4][8][16] bf16
   constexpr int TILE_BYTES = BM * BKM * 2;
-  constexpr int GRPS = TILE_BYTES / 1024;          // 1 KiB per wave-glds
-  constexpr int GRPS_PER_WAVE = GRPS / NWAVE;
-  constexpr int ROWS_PER_GRP = 1024 / 32;          // 32 m-rows per group
+  // 1 KiB per wave-glds; the two operands' images differ when BM != BN
+  constexpr int GRPS_A = TILE_BYTES / 1024 / NWAVE;
+  constexpr int GRPS_B = BN * BKM * 2 / 1024 / NWAVE;
+  static_assert(GRPS_A * NWAVE * 1024 == TILE_BYTES &&
+                    GRPS_B * NWAVE * 1024 == BN * BKM * 2,
+                "every wave stages whole 1-KiB groups of both images");
   __shared__ char smem[2 * (BM + BN) * BKM * 2];
   const auto lds_ab = [&](int i) { return smem + i * TILE_BYTES; };
   const auto lds_bb = [&](int i) {
@@ -1315,20 +1321,20 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
   const int c_end = min(m_full, c_beg + per_slice);
   if (c_beg >= c_end) return;
 
-  // panel-major glds staging: group g covers half a panel (32 m x 16 cols);
-  // lane's 16-B chunk = 8 columns of one m-row of the panel
+  // glds staging: group g covers one m octet of a 64-column group (8 m x
+  // 128 B, four [8][16] blocks); lane's 16-B chunk = 8 columns of one m-row
+  // of block lane / 16, so eight lanes fetch one whole 128-B line
   // (TAIL: the partial last step clamps the m-row to m - 1, so it stages
   // duplicates of a valid row and never reads past the tensor)
-  auto stage = [&]<bool TAIL = false>(const __bf16* src_base, long ld,
-                                      int col0, int mrow0, char* lds) {
+  auto stage = [&]<int GRPS_PER_WAVE, bool TAIL = false>(
+                   const __bf16* src_base, long ld, int col0, int mrow0,
+                   char* lds) {
 #pragma unroll
     for (int i = 0; i < GRPS_PER_WAVE; ++i) {
       const int grp = wave + i * NWAVE;
-      const int panel = grp / (PANEL_BYTES / 1024);
-      const int half = grp % (PANEL_BYTES / 1024);
-      int mrow = mrow0 + half * ROWS_PER_GRP + (lane >> 1);
+      int mrow = mrow0 + (grp % OCTS) * 8 + ((lane >> 1) & 7);
       if constexpr (TAIL) mrow = min(mrow, m - 1);
-      const int col = panel * 16 + (lane & 1) * 8;
+      const int col = (grp / OCTS) * 64 + (lane >> 4) * 16 + (lane & 1) * 8;
       const __bf16* src = src_base + (long)mrow * ld + col0 + col;
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)src,
@@ -1346,12 +1352,13 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
     for (int j = 0; j < FN; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
   }
 
-  stage(a, n, n0, c_beg, lds_ab(0));
-  stage(b, k2, k0, c_beg, lds_bb(0));
+  stage.template operator()<GRPS_A>(a, n, n0, c_beg, lds_ab(0));
+  stage.template operator()<GRPS_B>(b, k2, k0, c_beg, lds_bb(0));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  const bool do_bias = (dbias != nullptr) && (k0 == 0);
+  // wave-uniform: of the WCOL waves that read the same A fragments, one sums
+  const bool do_bias = (dbias != nullptr) && (k0 == 0) && wave % WCOL == 0;
 
   // fragment read via ds_read_b64_tr_b16: each 16-lane group passes
   // CONSECUTIVE 8-B addresses covering one 128-B [4 m][16 col] sub-tile;
@@ -1359,8 +1366,9 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
   // contract-consecutive elements.  Two reads (sub-tiles m+0..3, m+4..7)
   // assemble the 8-element MFMA k fragment.
   auto frag = [&](const char* img, int block16, int s) {
-    const char* p = img + (long)block16 * PANEL_BYTES +
-                    (s * 32 + ((lane >> 4) * 8)) * 32 + (lane & 15) * 8;
+    const char* p = img + (block16 >> 2) * GROUP_BYTES +
+                    (s * 4 + (lane >> 4)) * 1024 + (block16 & 3) * 256 +
+                    (lane & 15) * 8;
     bf16x4_g lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
         (__attribute__((address_space(3))) bf16x4_g*)p);
     bf16x4_g hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
@@ -1402,8 +1410,8 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
 
   int buf = 0;
   for (int cc = c_beg + BKM; cc < c_end; cc += BKM) {
-    stage(a, n, n0, cc, lds_ab(buf ^ 1));
-    stage(b, k2, k0, cc, lds_bb(buf ^ 1));
+    stage.template operator()<GRPS_A>(a, n, n0, cc, lds_ab(buf ^ 1));
+    stage.template operator()<GRPS_B>(b, k2, k0, cc, lds_bb(buf ^ 1));
     mma(lds_ab(buf), lds_bb(buf));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1416,28 +1424,30 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
   const int rem = m - m_full;
   const bool tail = rem > 0 && c_end == m_full;
   if (tail) {
-    stage.template operator()<true>(a, n, n0, m_full, lds_ab(buf ^ 1));
-    stage.template operator()<true>(b, k2, k0, m_full, lds_bb(buf ^ 1));
+    stage.template operator()<GRPS_A, true>(a, n, n0, m_full,
+                                            lds_ab(buf ^ 1));
+    stage.template operator()<GRPS_B, true>(b, k2, k0, m_full,
+                                            lds_bb(buf ^ 1));
   }
   mma(lds_ab(buf), lds_bb(buf));
   if (tail) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    // zero the rows >= rem of every [BKM][16] panel in BOTH images (32 B
-    // per row and panel): a zero on one side only would turn an Inf in the
-    // duplicated row of the other into a NaN
+    // zero the rows >= rem of every [8][16] block in BOTH images (32 B per
+    // row and block; 64 chunks of 16 B per octet): a zero on one side only
+    // would turn an Inf in the duplicated row of the other into a NaN
     const u32x4_t z = {0u, 0u, 0u, 0u};
     for (int t = threadIdx.x; t < (BM + BN) / 16 * BKM * 2; t += THREADS) {
       const bool in_b = t >= BM / 16 * BKM * 2;
       const int u = in_b ? t - BM / 16 * BKM * 2 : t;  // 16-B chunk in image
-      if ((u >> 1) % BKM >= rem)
+      if ((u >> 6) % OCTS * 8 + ((u & 15) >> 1) >= rem)
         *reinterpret_cast<u32x4_t*>(
             (in_b ? lds_bb(buf ^ 1) : lds_ab(buf ^ 1)) + u * 16) = z;
     }
     __syncthreads();
     mma(lds_ab(buf ^ 1), lds_bb(buf ^ 1));
   }
-  if (do_bias && wave % WCOL == 0) {
+  if (do_bias) {
 #pragma unroll
     for (int mi = 0; mi < FM; ++mi) {
       float v = dbacc[mi];
@@ -1473,32 +1483,67 @@ __global__ void gemm_a16_glds_tn_kernel(const __bf16* __restrict__ a,
 // allocates them) a single memset clears both.  `acc`: c and dbias are
 // gradient sinks that already hold a sum — nothing is cleared and every
 // element is added to.
-void launch_gemm_a16_glds_tn(const void* a_v, const void* b_v, float* c,
-                             float* dbias, int m, int n, int k2,
-                             hipStream_t s, bool acc) {
-  const __bf16* a = (const __bf16*)a_v;
-  const __bf16* b = (const __bf16*)b_v;
-  constexpr int BM = 128, BN = 128, BKM = 64;
+//
+// Output tile: gemm_dispatch::glds_tn_tile() picks it (128x128 today); `tile`
+// forces 128x128, 256x128 or 256x256 (TN_AUTO: the dispatch's choice), and
+// set_glds_tn_tile() moves the automatic choice for A/B runs and tests.
+static int g_glds_tn_tile = gemm_dispatch::TN_AUTO;  // test hook
+void set_glds_tn_tile(int tile) { g_glds_tn_tile = tile; }
+
+int glds_tn_tile_for(int m, int n, int k2, int tile) {
+  namespace gd = gemm_dispatch;
+  // a tile asked for by the caller must fit the shape (-1 otherwise) ...
+  if (tile != gd::TN_AUTO)
+    return gd::glds_tn_tile_ok(tile, m, n, k2) ? tile : -1;
+  // ... a process-wide override applies where it fits
+  if (g_glds_tn_tile != gd::TN_AUTO &&
+      gd::glds_tn_tile_ok(g_glds_tn_tile, m, n, k2))
+    return g_glds_tn_tile;
+  return gd::glds_tn_tile(m, n, k2);
+}
+
+template <int BM, int BN>
+static void launch_glds_tn_tile(const __bf16* a, const __bf16* b, float* c,
+                                float* dbias, int m, int n, int k2,
+                                hipStream_t s, bool acc) {
+  constexpr int BKM = 64;
   const int tiles = (n / BM) * (k2 / BN);
   // split-K over the full BKM steps; the tail step rides the last slice and
   // does not change the split (m and m - m % BKM slice alike)
   const int slices = gemm_dispatch::glds_tn_slices(m, tiles);
-  const long nc = (long)n * k2;
-  if (acc) {
+  if (acc)
     gemm_a16_glds_tn_kernel<BM, BN, BKM, 512, true>
         <<<dim3(tiles * slices), dim3(512), 0, s>>>(a, b, c, dbias, m, n, k2,
                                                     slices);
-    return;
+  else
+    gemm_a16_glds_tn_kernel<BM, BN, BKM>
+        <<<dim3(tiles * slices), dim3(512), 0, s>>>(a, b, c, dbias, m, n, k2,
+                                                    slices);
+}
+
+void launch_gemm_a16_glds_tn(const void* a_v, const void* b_v, float* c,
+                             float* dbias, int m, int n, int k2,
+                             hipStream_t s, bool acc, int tile) {
+  namespace gd = gemm_dispatch;
+  const __bf16* a = (const __bf16*)a_v;
+  const __bf16* b = (const __bf16*)b_v;
+  const long nc = (long)n * k2;
+  if (!acc) {
+    if (dbias == c + nc) {
+      HIP_CHECK(hipMemsetAsync(c, 0, (nc + n) * sizeof(float), s));
+    } else {
+      HIP_CHECK(hipMemsetAsync(c, 0, nc * sizeof(float), s));
+      if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
+    }
   }
-  if (dbias == c + nc) {
-    HIP_CHECK(hipMemsetAsync(c, 0, (nc + n) * sizeof(float), s));
-  } else {
-    HIP_CHECK(hipMemsetAsync(c, 0, nc * sizeof(float), s));
-    if (dbias) HIP_CHECK(hipMemsetAsync(dbias, 0, n * sizeof(float), s));
+  switch (glds_tn_tile_for(m, n, k2, tile)) {
+    case gd::TN_256x256:
+      return launch_glds_tn_tile<256, 256>(a, b, c, dbias, m, n, k2, s, acc);
+    case gd::TN_256x128:
+      return launch_glds_tn_tile<256, 128>(a, b, c, dbias, m, n, k2, s, acc);
+    default:
+      return launch_glds_tn_tile<128, 128>(a, b, c, dbias, m, n, k2, s, acc);
   }
-  gemm_a16_glds_tn_kernel<BM, BN, BKM>
-      <<<dim3(tiles * slices), dim3(512), 0, s>>>(a, b, c, dbias, m, n, k2,
-                                                  slices);
 }
 
 // ---------------------------------------------------------------------------

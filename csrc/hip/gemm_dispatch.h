@@ -69,6 +69,33 @@ inline int glds_tn_slices(int m, int tiles) {
   return slices;
 }
 
+// Output tile of the glds TN kernel, rows (of n) x columns (of k).
+enum TnTile { TN_AUTO = 0, TN_128x128 = 1, TN_256x128 = 2, TN_256x256 = 3 };
+
+inline int tn_tile_rows(int tile) { return tile == TN_128x128 ? 128 : 256; }
+inline int tn_tile_cols(int tile) { return tile == TN_256x256 ? 256 : 128; }
+inline const char* tn_tile_name(int tile) {
+  return tile == TN_256x256 ? "256x256"
+         : tile == TN_256x128 ? "256x128" : "128x128";
+}
+
+// whether the glds TN kernel can run this shape with this tile
+inline bool glds_tn_tile_ok(int tile, int m, int n, int k) {
+  return tile >= TN_128x128 && tile <= TN_256x256 && m >= 512 &&
+         n % tn_tile_rows(tile) == 0 && k % tn_tile_cols(tile) == 0;
+}
+
+// The tile the glds TN kernel takes by default: 128x128 at every shape.  The
+// wide tiles stage each operand row block half as often, but at one block
+// per CU they lose more in latency hiding than they save in staged bytes
+// (measured at [180k, 1024]^T x [180k, 256] and at 45k rows:
+// profiles/21_wgrad_tiles.md), so they run only where a caller forces them.
+inline int glds_tn_tile(int /*m*/, int /*n*/, int /*k*/) { return TN_128x128; }
+
+inline int glds_tn_tiles(int tile, int n, int k) {
+  return (n / tn_tile_rows(tile)) * (k / tn_tile_cols(tile));
+}
+
 // one-wave-per-strip NN kernel for the tiny-row dgrad (fp32 x, bf16 g)
 inline bool dgrad_skinny(int m) { return m <= 16; }
 
