@@ -95,6 +95,8 @@ void launch_embed_node_fwd(const float*, const long*, const float*, float*,
                            long, int, int, hipStream_t);
 void launch_embed_node_fwd16(const float*, const long*, const float*, void*,
                              long, int, int, hipStream_t);
+void launch_embed_node_pad(const float*, const long*, const float*, void*, int,
+                           long, int, int, int, hipStream_t);
 void launch_vocab_scatter16(const void*, const long*, long, float*, long, int,
                             int, int, int, hipStream_t);
 void launch_embed_edge_fwd(const long*, const float*, const float*, float*,
@@ -236,7 +238,8 @@ void launch_edge_attn_fused_bwd16(const void*, int, const void*,
                                   int, const float*, const int*, const int*,
                                   const int*, const int*, const int*, void*,
                                   void*, float*, int, int, long, int,
-                                  hipStream_t, const AttnBnBwd* = nullptr);
+                                  hipStream_t, const AttnBnBwd* = nullptr,
+                                  const AttnPoolBwd* = nullptr);
 void launch_bn_bwd_partials_affine16(const void*, const void*,
                                      const unsigned char*, const float*,
                                      const float*, long, int, float*, float,
@@ -378,11 +381,24 @@ torch::Tensor seg_pool_bwd(torch::Tensor gout, torch::Tensor probs,
 }
 
 torch::Tensor embed_node_fwd(torch::Tensor x_raw, torch::Tensor idx,
-                             torch::Tensor table, bool out16 = false) {
+                             torch::Tensor table, bool out16 = false,
+                             int64_t pad_to = 0) {
   CHECK_IN(x_raw); CHECK_IN(idx); CHECK_IN(table);
   const long n = x_raw.size(0);
   const int f = x_raw.size(1);
   const int h = table.size(1);
+  if (pad_to != 0) {
+    // [n, pad_to]: the concat in the first f + h columns, +0 in the rest
+    TORCH_CHECK(pad_to >= f + h && pad_to <= INT_MAX,
+                "embed_node_fwd: pad_to=", pad_to, " is below f + h = ", f + h);
+    auto out = torch::empty(
+        {n, pad_to}, out16 ? x_raw.options().dtype(torch::kBFloat16)
+                           : x_raw.options());
+    launch_embed_node_pad(x_raw.data_ptr<float>(), idx.data_ptr<long>(),
+                          table.data_ptr<float>(), out.data_ptr(),
+                          out16 ? 1 : 0, n, f, h, (int)pad_to, cur_stream());
+    return out;
+  }
   if (out16) {
     auto out = torch::empty({n, f + h},
                             x_raw.options().dtype(torch::kBFloat16));
@@ -1527,6 +1543,61 @@ std::vector<torch::Tensor> edge_attn_bn_bwd16(
   return {dqkvs, de, aff.dgamma, aff.dbeta};
 }
 
+// Backward of edge_attention_fused (bf16 qkvs, fp32 output) whose only
+// upstream gradient is the pattern pool's: gout [graphs, h] is the gradient
+// of the pooled output and the kernels form g[i] = gout[batch[i]] * probs[i]
+// / nn[i] themselves.  -> {dqkvs, de}, the bits of seg_pool_bwd followed by
+// edge_attn_fused_bwd, without the [n, h] gradient in between.
+std::vector<torch::Tensor> edge_attn_pool_bwd16(
+    torch::Tensor gout, torch::Tensor probs, torch::Tensor nn,
+    torch::Tensor batch, torch::Tensor qkvs, torch::Tensor pifc,
+    torch::Tensor prpc, torch::Tensor ea, torch::Tensor alpha,
+    torch::Tensor row_ptr, torch::Tensor csr_src, torch::Tensor col_ptr,
+    torch::Tensor csc_dst, torch::Tensor csc_eid, int64_t heads = 1) {
+  CHECK_IN(gout); CHECK_IN(probs); CHECK_IN(nn); CHECK_IN(batch);
+  CHECK_IN(qkvs); CHECK_IN(alpha);
+  const int n = qkvs.size(0);
+  const int h = qkvs.size(1) / 4;
+  const long ne = ea.size(0);
+  TORCH_CHECK(h == 256 || h == 512, "edge_attn_pool_bwd16 covers H = 256, 512");
+  TORCH_CHECK(qkvs.scalar_type() == torch::kBFloat16,
+              "edge_attn_pool_bwd16 takes bf16 qkvs");
+  TORCH_CHECK(gout.scalar_type() == torch::kFloat32 && gout.dim() == 2 &&
+                  gout.size(1) == h,
+              "gout must be fp32 [graphs, h]");
+  TORCH_CHECK(probs.scalar_type() == torch::kFloat32 &&
+                  nn.scalar_type() == torch::kFloat32 &&
+                  batch.scalar_type() == torch::kInt64 &&
+                  probs.numel() == n && nn.numel() == n && batch.numel() == n,
+              "probs/nn (fp32) and batch (int64) must have one entry per node");
+  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
+              "heads must divide H (H=", h, ", heads=", heads, ")");
+  TORCH_CHECK(alpha.scalar_type() == torch::kFloat32 &&
+                  alpha.numel() == ne * heads,
+              "alpha must be the fp32 [E, heads] tensor of the forward");
+  TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(),
+              "P tables must share a dtype");
+  AttnPoolBwd pool{};
+  pool.gout = gout.data_ptr<float>();
+  pool.probs = probs.data_ptr<float>();
+  pool.nn = nn.data_ptr<float>();
+  pool.batch = batch.data_ptr<long>();
+  auto fopt = qkvs.options().dtype(torch::kFloat32);
+  auto dqkvs = torch::empty_like(qkvs);
+  auto de = torch::empty({ne, h}, qkvs.options());
+  auto dal = torch::empty({ne * heads}, fopt);
+  const int p16 = pifc.scalar_type() == torch::kBFloat16 ? 1 : 0;
+  launch_edge_attn_fused_bwd16(
+      nullptr, 0, qkvs.data_ptr(), pifc.data_ptr(), prpc.data_ptr(), p16,
+      ea.data_ptr<long>(), (int)ea.size(1), alpha.data_ptr<float>(),
+      row_ptr.data_ptr<int>(), csr_src.data_ptr<int>(),
+      col_ptr.data_ptr<int>(), csc_dst.data_ptr<int>(),
+      csc_eid.data_ptr<int>(), dqkvs.data_ptr(), de.data_ptr(),
+      dal.data_ptr<float>(), n, h, ne, (int)heads, cur_stream(), nullptr,
+      &pool);
+  return {dqkvs, de};
+}
+
 torch::Tensor seg_pool_fwd16(torch::Tensor x, torch::Tensor probs,
                              torch::Tensor nn, torch::Tensor batch_ptr,
                              int64_t num_graphs) {
@@ -2115,7 +2186,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("edge_attn_bwd", &edge_attn_bwd);
   mod.def("seg_pool_fwd", &seg_pool_fwd);
   mod.def("seg_pool_bwd", &seg_pool_bwd);
-  mod.def("embed_node_fwd", &embed_node_fwd, py::arg("x_raw"), py::arg("idx"), py::arg("table"), py::arg("out16") = false);
+  mod.def("embed_node_fwd", &embed_node_fwd, py::arg("x_raw"), py::arg("idx"), py::arg("table"), py::arg("out16") = false, py::arg("pad_to") = 0);
   mod.def("embed_edge_fwd", &embed_edge_fwd);
   mod.def("gather_rows", &gather_rows);
   mod.def("bn_relu_fwd16", &bn_relu_fwd16, py::arg("x"), py::arg("gamma"),
@@ -2152,6 +2223,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("partials_local") = py::none(),
           py::arg("dgamma_sink") = py::none(),
           py::arg("dbeta_sink") = py::none());
+  mod.def("edge_attn_pool_bwd16", &edge_attn_pool_bwd16, py::arg("gout"),
+          py::arg("probs"), py::arg("nn"), py::arg("batch"), py::arg("qkvs"),
+          py::arg("pifc"), py::arg("prpc"), py::arg("edge_attr"),
+          py::arg("alpha"), py::arg("row_ptr"), py::arg("csr_src"),
+          py::arg("col_ptr"), py::arg("csc_dst"), py::arg("csc_eid"),
+          py::arg("heads") = 1);
   mod.def("seg_pool_fwd16", &seg_pool_fwd16);
   mod.def("seg_pool_bwd16", &seg_pool_bwd16);
   mod.def("linear_fwd_a16o16", &linear_fwd_a16o16, py::arg("x"), py::arg("w"),

@@ -14,3 +14,14 @@ struct AttnBnBwd {
   long count;                 // row count used when count_ptr is null
   float keep_inv;             // 1/(1-p) of the fused dropout, 1 without
 };
+
+// Argument pack of the pattern-pool backward that the last conv's attention
+// backward forms itself: the gradient of node i is gout[batch[i]] * probs[i] /
+// nn[i] (pool_bwd_dx in common.h), so neither kernel reads an [n, h] gradient.
+// A null gout means off.
+struct AttnPoolBwd {
+  const float* gout;   // [graphs, h]: gradient of the pooled output
+  const float* probs;  // [n]
+  const float* nn;     // [n]
+  const long* batch;   // [n]: graph of each node
+};

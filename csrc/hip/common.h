@@ -66,6 +66,15 @@ __device__ __forceinline__ __bf16 bn_bwd_dx16(float g, float x, bool keep,
                   __builtin_fmaf(-invn, xhat * p1, gm - p0 * invn));
 }
 
+// One element of the pattern pool's input gradient, gout * p / n: the product
+// first, then an IEEE division (no pre-divided p / n, no reciprocal).
+// seg_pool_bwd_kernel and the pool mode of the fused attention backward both
+// inline this, so they give the same bits for the same inputs.
+__device__ __forceinline__ float pool_bwd_dx(float gout, float p, float n) {
+#pragma clang fp contract(off)
+  return (gout * p) / n;
+}
+
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // XCD-aware blockIdx remap (guide §5.5 T1, bijective form): the dispatcher

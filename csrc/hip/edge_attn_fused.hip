@@ -466,16 +466,41 @@ __device__ __forceinline__ void attn_bn_bwd_row(const AttnBnBwd& bn, int row,
   }
 }
 
+// Pattern-pool backward of one node's row slice: the fp32 values that
+// seg_pool_bwd_kernel would have stored at [node, lane's channels].
+template <int VPT>
+__device__ __forceinline__ void attn_pool_bwd_row(const AttnPoolBwd& pool,
+                                                  long node, int lane, int h,
+                                                  float (&gr)[VPT]) {
+  const float p = pool.probs[node];
+  const float nn = pool.nn[node];
+  Slice<VPT, true>::load(&pool.gout[pool.batch[node] * h], lane, h, gr);
+#pragma unroll
+  for (int j = 0; j < VPT; ++j) gr[j] = pool_bwd_dx(gr[j], p, nn);
+}
+
+// POOL (both backward kernels): there is no g; a node's gradient is the
+// pattern pool's backward, formed from `pool`.  Only the instantiations the
+// last conv takes in act16 mode carry it (fp32 gradient, bf16 qkvs, VEC
+// mapping).  A template parameter and not a branch on pool.gout: with both
+// paths in one kernel the col kernel's edge loop held the registers of both
+// gathers (62 -> 91 VGPRs at H = 256, three waves per SIMD lost).
+template <bool POOL, bool VEC, typename QT, typename TG>
+constexpr bool attn_pool_ok =
+    !POOL ||
+    (VEC && std::is_same<TG, float>::value && std::is_same<QT, __bf16>::value);
+
 template <int VPT, bool VEC, typename QT = float,
           int LPR = PERTGNN_WAVE, typename TG = float, typename PT = float,
-          int LPH = LPR, bool PCH = false>
+          int LPH = LPR, bool PCH = false, bool POOL = false>
 __global__ void edge_attn_fused_bwd_row_kernel(
     const TG* __restrict__ g, const QT* __restrict__ qkvs,
     const PT* __restrict__ pifc, const PT* __restrict__ prpc,
     const long* __restrict__ ea, int astride, const float* __restrict__ alpha,
     const int* __restrict__ row_ptr, const int* __restrict__ csr_src,
     QT* __restrict__ dqkvs, float* __restrict__ dal, int n, int h,
-    float scale, AttnBnBwd bn = AttnBnBwd{}) {
+    float scale, AttnBnBwd bn = AttnBnBwd{},
+    AttnPoolBwd pool = AttnPoolBwd{}) {
   // SINGLE pass over the row's edges (the old two-pass form re-gathered
   // ec+ke per edge after sdot was known).  Softmax backward re-expressed:
   //   dq = scale * (Sum a*da*(k+e)  -  sdot * Sum a*(k+e))
@@ -499,7 +524,11 @@ __global__ void edge_attn_fused_bwd_row_kernel(
   const long ld = 4L * h;
 
   float gr[VPT], a1[VPT], a2[VPT];
-  S::load(&g[(long)row * h], lane, h, gr);
+  static_assert(attn_pool_ok<POOL, VEC, QT, TG>, "pool mode: act16, fp32 g");
+  // POOL: the row's gradient is the pattern pool's backward, formed here
+  // and stored as dskip below like any other
+  if constexpr (POOL) attn_pool_bwd_row<VPT>(pool, row, lane, h, gr);
+  else S::load(&g[(long)row * h], lane, h, gr);
   // g is the BN OUTPUT gradient when bn.x is set (wave-uniform): the row's
   // gradient is then formed here, and stored as dskip below like any other
   // (h = 256 / 512 only: VPT <= 16 in every lane mapping of those widths)
@@ -597,13 +626,14 @@ __global__ void edge_attn_fused_bwd_row_kernel(
 
 template <int VPT, bool VEC, typename QT = float, typename ET = float,
           int LPR = PERTGNN_WAVE, typename TG = float, int LPH = LPR,
-          bool PCH = false>
+          bool PCH = false, bool POOL = false>
 __global__ void edge_attn_fused_bwd_col_kernel(
     const TG* g, const QT* __restrict__ qkvs,
     const float* __restrict__ alpha, const float* __restrict__ dal,
     const int* __restrict__ col_ptr, const int* __restrict__ csc_dst,
     const int* __restrict__ csc_eid, QT* dqkvs,
-    ET* __restrict__ de, int n, int h, long gld) {
+    ET* __restrict__ de, int n, int h, long gld,
+    AttnPoolBwd pool = AttnPoolBwd{}) {
   // g rows lie gld elements apart: h for a compact [n, h] gradient, 4h when
   // g is the dskip segment of dqkvs that the row kernel wrote before this
   // kernel started (same stream).  g and dqkvs then share an allocation —
@@ -615,6 +645,7 @@ __global__ void edge_attn_fused_bwd_col_kernel(
                 "heads split the sub-row (VEC) or the columns (PCH)");
   static_assert(LPH >= 1 && LPH <= LPR && (LPH & (LPH - 1)) == 0,
                 "lanes per head: a power of two within the row");
+  static_assert(attn_pool_ok<POOL, VEC, QT, TG>, "pool mode: act16, fp32 g");
   constexpr int RPW = PERTGNN_WAVE / LPR;
   const int wid = threadIdx.x / PERTGNN_WAVE;
   const int lane0 = threadIdx.x % PERTGNN_WAVE;
@@ -661,7 +692,10 @@ __global__ void edge_attn_fused_bwd_col_kernel(
     const float a = alpha[eid * HM::HEADS + hd];
     float qd[VPT], gd[VPT], des[VPT];
     S::load(&qkvs[dst * ld], lane, h, qd);
-    S::load(&g[dst * gld], lane, h, gd);
+    // pool mode: the destination's gradient from its graph's gout row and
+    // its two scalars, the same bits the row kernel formed for that node
+    if constexpr (POOL) attn_pool_bwd_row<VPT>(pool, dst, lane, h, gd);
+    else S::load(&g[dst * gld], lane, h, gd);
 #pragma unroll
     for (int j = 0; j < VPT; ++j) {
       const float dk1 = dl * qd[j];
@@ -984,10 +1018,17 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
                                   const int* csc_dst, const int* csc_eid,
                                   void* dqkvs_v, void* de_v, float* dal,
                                   int n, int h, long num_edges, int heads,
-                                  hipStream_t stream, const AttnBnBwd* bn) {
+                                  hipStream_t stream, const AttnBnBwd* bn,
+                                  const AttnPoolBwd* pool) {
   const __bf16* qkvs = (const __bf16*)qkvs_v;
   __bf16* dqkvs = (__bf16*)dqkvs_v;
   __bf16* de = (__bf16*)de_v;
+  // pool (may be null): there is no g_v; both kernels form the fp32 gradient
+  // of a node from the pattern pool's backward (the fp32-g branches only)
+  if (pool && (g16 || bn))
+    pertgnn_shape_fail("edge_attn_fused act16 launcher",
+                       bn ? "pool with bn, h" : "pool with bf16 g, h", h);
+  const AttnPoolBwd poolk = pool ? *pool : AttnPoolBwd{};
   // bn (may be null): g_v is the gradient of the BN OUTPUT; the row kernel
   // applies the BN backward to each row it loads and the col kernel gathers
   // the result from the dskip columns the row kernel wrote (bf16 g only)
@@ -1005,6 +1046,21 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
   const int rpb = WAVES_PER_BLOCK * (PERTGNN_WAVE / lpr);
   const dim3 grid(ceil_div(n, rpb));
   const char* name = "edge_attn_fused act16 launcher";
+// fp32 (or, POOL, no) upstream gradient: the last conv's backward
+#define BWD16_G32(VPT, LPR, LPH, PT, POOL)                                     \
+  do {                                                                         \
+    edge_attn_fused_bwd_row_kernel<VPT, true, __bf16, LPR, float, PT, LPH,     \
+                                   false, POOL>                                \
+        <<<grid, block, 0, stream>>>((const float*)g_v, qkvs,                  \
+                                     (const PT*)pifc_v, (const PT*)prpc_v, ea, \
+                                     astride, alpha, row_ptr, csr_src, dqkvs,  \
+                                     dal, n, h, scale, AttnBnBwd{}, poolk);    \
+    edge_attn_fused_bwd_col_kernel<VPT, true, __bf16, __bf16, LPR, float,      \
+                                   LPH, false, POOL>                           \
+        <<<grid, block, 0, stream>>>((const float*)g_v, qkvs, alpha, dal,      \
+                                     col_ptr, csc_dst, csc_eid, dqkvs, de, n,  \
+                                     h, h, poolk);                             \
+  } while (0)
 #define BWD16(VPT, LPR, LPH)                                                   \
   do {                                                                         \
     if (n == 0) break;                                                         \
@@ -1037,31 +1093,11 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
     } else if (p16) {                                                          \
       /* fp32 upstream grad (the last conv's out16=false) + bf16 P tables — \
          reading the tables at the wrong width over-reads 2x (OOB) */        \
-      edge_attn_fused_bwd_row_kernel<VPT, true, __bf16, LPR, float, __bf16,    \
-                                     LPH>                                      \
-          <<<grid, block, 0, stream>>>((const float*)g_v, qkvs,                \
-                                       (const __bf16*)pifc_v,                  \
-                                       (const __bf16*)prpc_v,                  \
-                                       ea, astride, alpha, row_ptr, csr_src,   \
-                                       dqkvs, dal, n, h, scale);               \
-      edge_attn_fused_bwd_col_kernel<VPT, true, __bf16, __bf16, LPR, float,    \
-                                     LPH>                                      \
-          <<<grid, block, 0, stream>>>((const float*)g_v, qkvs, alpha, dal,    \
-                                       col_ptr, csc_dst, csc_eid, dqkvs, de,   \
-                                       n, h, h);                               \
+      if (pool) BWD16_G32(VPT, LPR, LPH, __bf16, true);                        \
+      else BWD16_G32(VPT, LPR, LPH, __bf16, false);                            \
     } else {                                                                   \
-      edge_attn_fused_bwd_row_kernel<VPT, true, __bf16, LPR, float, float,     \
-                                     LPH>                                      \
-          <<<grid, block, 0, stream>>>((const float*)g_v, qkvs,                \
-                                       (const float*)pifc_v,                   \
-                                       (const float*)prpc_v,                   \
-                                       ea, astride, alpha, row_ptr, csr_src,   \
-                                       dqkvs, dal, n, h, scale);               \
-      edge_attn_fused_bwd_col_kernel<VPT, true, __bf16, __bf16, LPR, float,    \
-                                     LPH>                                      \
-          <<<grid, block, 0, stream>>>((const float*)g_v, qkvs, alpha, dal,    \
-                                       col_ptr, csc_dst, csc_eid, dqkvs, de,   \
-                                       n, h, h);                               \
+      if (pool) BWD16_G32(VPT, LPR, LPH, float, true);                         \
+      else BWD16_G32(VPT, LPR, LPH, float, false);                             \
     }                                                                          \
   } while (0)
 #define BWD16_H(VPT, LPR)                                                      \
@@ -1085,6 +1121,7 @@ void launch_edge_attn_fused_bwd16(const void* g_v, int g16,
   }
 #undef BWD16_H
 #undef BWD16
+#undef BWD16_G32
 }
 
 

@@ -86,7 +86,7 @@ __global__ void seg_pool_bwd_kernel(const float* __restrict__ gout,
   for (long t = i; t < numel; t += stride) {
     const long row = t / h;
     const int c = (int)(t - row * h);
-    dx[t] = (TD)(gout[batch[row] * h + c] * probs[row] / nn[row]);
+    dx[t] = (TD)pool_bwd_dx(gout[batch[row] * h + c], probs[row], nn[row]);
   }
 }
 
@@ -176,6 +176,56 @@ __global__ void embed_node_fwd_kernel(const float* __restrict__ x_raw,
     const int c = (int)(t - row * w);
     out[t] = (TY)((c < f) ? x_raw[row * f + c]
                           : table[idx[row] * h + (c - f)]);
+  }
+}
+
+// embed_node_fwd with the row padded to pad_to >= f + h columns (+0 past
+// f + h): the layer-1 GEMM operand at its staging width, written once.
+// LPR lanes share a row, so the row index and idx[row] are uniform over the
+// sub-wave and nothing is divided per element.  EPC > 1: each lane builds
+// EPC consecutive columns (16 B) in registers and stores them whole; the
+// launcher guarantees pad_to % EPC == 0, so every row starts 16-B aligned.
+// Table rows are only 4-B aligned relative to a chunk (f is arbitrary), so
+// they are read by dword.  EPC == 1 is the scalar path for any other pad_to.
+template <typename TY, int EPC, int LPR>
+__global__ void embed_node_pad_kernel(const float* __restrict__ x_raw,
+                                      const long* __restrict__ idx,
+                                      const float* __restrict__ table,
+                                      TY* __restrict__ out, long n, int f,
+                                      int h, int pad_to) {
+  typedef __attribute__((ext_vector_type(EPC))) TY chunk_t;
+  constexpr int RPW = PERTGNN_WAVE / LPR;
+  const int lane0 = threadIdx.x % PERTGNN_WAVE;
+  const int lane = lane0 % LPR;
+  const long wave = ((long)blockIdx.x * blockDim.x + threadIdx.x) / PERTGNN_WAVE;
+  const long waves = (long)gridDim.x * blockDim.x / PERTGNN_WAVE;
+  const int w = f + h;
+  for (long row = wave * RPW + lane0 / LPR; row < n; row += waves * RPW) {
+    const float* xr = x_raw + row * f;
+    const float* tr = table + idx[row] * h;
+    TY* orow = out + row * pad_to;
+    for (int c0 = lane * EPC; c0 < pad_to; c0 += LPR * EPC) {
+      float v[EPC];
+      if (c0 >= f && c0 + EPC <= w) {
+#pragma unroll
+        for (int u = 0; u < EPC; ++u) v[u] = tr[c0 - f + u];
+      } else {
+        // the raw/table seam or the table/pad seam falls inside this chunk
+#pragma unroll
+        for (int u = 0; u < EPC; ++u) {
+          const int c = c0 + u;
+          v[u] = (c < f) ? xr[c] : (c < w) ? tr[c - f] : 0.f;
+        }
+      }
+      if constexpr (EPC == 1) {
+        orow[c0] = (TY)v[0];
+      } else {
+        chunk_t o;
+#pragma unroll
+        for (int u = 0; u < EPC; ++u) o[u] = (TY)v[u];
+        *reinterpret_cast<chunk_t*>(orow + c0) = o;
+      }
+    }
   }
 }
 
@@ -1034,6 +1084,53 @@ void launch_embed_node_fwd16(const float* x_raw, const long* idx,
   embed_node_fwd_kernel<<<dim3(blocks), dim3(tpb), 0, stream>>>(
       x_raw, idx, table, (__bf16*)out, n, f, h);
 }
+
+// padded output [n, pad_to], pad_to >= f + h (checked by the binding)
+template <typename TY, int EPC>
+static void embed_node_pad_launch(const float* x_raw, const long* idx,
+                                  const float* table, TY* out, long n, int f,
+                                  int h, int pad_to, hipStream_t s) {
+  // lanes per row: the sub-wave width that wastes the fewest lane slots on
+  // the row's pad_to / EPC chunks, the widest on a tie
+  const int chunks = pad_to / EPC;
+  int lpr = PERTGNN_WAVE;
+  for (int l = PERTGNN_WAVE; l >= 8; l /= 2)
+    if (ceil_div(chunks, l) * l < ceil_div(chunks, lpr) * lpr) lpr = l;
+  const int tpb = 256;
+  const long rows_per_block = (long)(tpb / PERTGNN_WAVE) * (PERTGNN_WAVE / lpr);
+  const dim3 grid((unsigned)min((n + rows_per_block - 1) / rows_per_block,
+                                (long)8192));
+#define LAUNCH(L)                                                              \
+  embed_node_pad_kernel<TY, EPC, L>                                            \
+      <<<grid, dim3(tpb), 0, s>>>(x_raw, idx, table, out, n, f, h, pad_to)
+  if (lpr == 64) LAUNCH(64);
+  else if (lpr == 32) LAUNCH(32);
+  else if (lpr == 16) LAUNCH(16);
+  else LAUNCH(8);
+#undef LAUNCH
+}
+
+void launch_embed_node_pad(const float* x_raw, const long* idx,
+                           const float* table, void* out, int out16, long n,
+                           int f, int h, int pad_to, hipStream_t s) {
+  if (n == 0) return;
+  if (out16) {
+    if (pad_to % 8 == 0)
+      embed_node_pad_launch<__bf16, 8>(x_raw, idx, table, (__bf16*)out, n, f,
+                                       h, pad_to, s);
+    else
+      embed_node_pad_launch<__bf16, 1>(x_raw, idx, table, (__bf16*)out, n, f,
+                                       h, pad_to, s);
+  } else {
+    if (pad_to % 4 == 0)
+      embed_node_pad_launch<float, 4>(x_raw, idx, table, (float*)out, n, f, h,
+                                      pad_to, s);
+    else
+      embed_node_pad_launch<float, 1>(x_raw, idx, table, (float*)out, n, f, h,
+                                      pad_to, s);
+  }
+}
+
 void launch_embed_edge_fwd(const long* attr, const float* ifc,
                            const float* rpc, float* out, long e, int h,
                            int astride, hipStream_t s) {

@@ -140,7 +140,7 @@ class Predictor:
         act16 = self._act16 and use_hip(b.x)
         x = ops.embed_concat_node(b.x, b.cat_X,
                                   [t.weight for t in m.cat_embedding],
-                                  out16=act16)
+                                  out16=act16, pad_to=m.convs[0].k_padded)
         last = len(m.convs) - 1
         for i, conv in enumerate(m.convs):
             if x.shape[1] != conv.k_padded:

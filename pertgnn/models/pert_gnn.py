@@ -237,6 +237,19 @@ class TransformerConv(nn.Module):
             bn.running_mean, bn.running_var, bn.momentum, bn.eps,
             heads=self.heads, comm=comm, dropout_p=dropout_p)
 
+    def forward_fused_pool(self, x, edge_attr, ifc_weight, rpc_weight, csr,
+                           probs, nnodes, batch, num_graphs, pifc=None,
+                           prpc=None):
+        """``forward_fused(...)`` (fp32 out) and the pattern pool over it ->
+        ``(x, mean_x)``: one autograd node where ``ops.pool_attn_fuse_enabled``
+        holds, whose backward forms the pool's gradient inside the attention
+        backward; the two separate ops otherwise."""
+        qkvs, pifc, prpc = self._fused_operands(x, ifc_weight, rpc_weight,
+                                                pifc, prpc)
+        return ops.edge_attention_fused_pool(
+            qkvs, pifc, prpc, edge_attr, csr, probs, nnodes, batch,
+            num_graphs, heads=self.heads)
+
     def _fused_operands(self, x, ifc_weight, rpc_weight, pifc, prpc):
         """qkvs and the two P tables of the fused attention op."""
         h = self.out_channels
@@ -366,9 +379,12 @@ class SAGEDeterministic(nn.Module):
         hidden = self.bns[0].weight.shape[0] if len(self.bns) else 0
         out16 = (fused and ops.gemm_precision() in ("bf16", "fp16")
                  and hidden % 256 == 0 and ops.act16_enabled())
+        # fused path: the concat comes out at the first conv's padded GEMM
+        # width, so forward_fused finds nothing left to pad
         x = ops.embed_concat_node(x, cat_X,
                                   [t.weight for t in self.cat_embedding],
-                                  out16=out16)
+                                  out16=out16,
+                                  pad_to=self.convs[0].k_padded if fused else None)
         edge_embeds = None
         if not fused:
             edge_embeds = ops.embed_concat_edge(
@@ -426,9 +442,20 @@ class SAGEDeterministic(nn.Module):
                 )
             if self.training and bn.track_running_stats and bn.num_batches_tracked is not None:
                 bn.num_batches_tracked += 1
-        x = run_conv(self.convs[-1], x)
+        if fused:
+            # last conv + pool as one op: a loss on global_predict alone
+            # then never spreads the pool's gradient over [N, H]
+            conv = self.convs[-1]
+            pifc, prpc = ptables.get(id(conv), (None, None))
+            x, mean_x = conv.forward_fused_pool(
+                x, edge_attr, self.interface_embeds.weight,
+                self.rpctype_embeds.weight, csr, pattern_probs,
+                pattern_num_nodes, batch, num_graphs, pifc=pifc, prpc=prpc)
+        else:
+            x = run_conv(self.convs[-1], x)
+            mean_x = ops.pattern_pool(x, pattern_probs, pattern_num_nodes,
+                                      batch, num_graphs)
         local_predict = ops.linear(x, self.local_linear.weight, self.local_linear.bias)
-        mean_x = ops.pattern_pool(x, pattern_probs, pattern_num_nodes, batch, num_graphs)
         entry_vec = ops.embedding(entry_id, self.entry_embeds.weight)
         global_predict = torch.cat([mean_x, entry_vec], dim=1)
         h = ops.linear(global_predict, self.global_linear1.weight, self.global_linear1.bias)

@@ -724,18 +724,23 @@ def edge_attention_fused_infer(qkvs, pifc, prpc, edge_attr, csr,
 # pattern pool (K9+K10)
 # ---------------------------------------------------------------------------
 
+def _pool_forward(m, x, probs, nnodes, batch, num_graphs):
+    """The pattern pool's forward launches (shared by its two autograd
+    nodes)."""
+    # nodes are contiguous per graph (collation order) -> batch_ptr.
+    # scatter_add instead of bincount: bincount syncs on the device max,
+    # which would break hipGraph capture of the training step.
+    counts = torch.zeros(num_graphs, dtype=torch.long, device=x.device)
+    counts.scatter_add_(0, batch, torch.ones_like(batch))
+    batch_ptr = torch.zeros(num_graphs + 1, dtype=torch.int32, device=x.device)
+    batch_ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    return m.seg_pool_fwd(x, probs.contiguous(), nnodes.contiguous(), batch_ptr, num_graphs)
+
+
 class _PatternPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, probs, nnodes, batch, num_graphs):
-        m = ext()
-        # nodes are contiguous per graph (collation order) -> batch_ptr.
-        # scatter_add instead of bincount: bincount syncs on the device max,
-        # which would break hipGraph capture of the training step.
-        counts = torch.zeros(num_graphs, dtype=torch.long, device=x.device)
-        counts.scatter_add_(0, batch, torch.ones_like(batch))
-        batch_ptr = torch.zeros(num_graphs + 1, dtype=torch.int32, device=x.device)
-        batch_ptr[1:] = torch.cumsum(counts, 0).to(torch.int32)
-        out = m.seg_pool_fwd(x, probs.contiguous(), nnodes.contiguous(), batch_ptr, num_graphs)
+        out = _pool_forward(ext(), x, probs, nnodes, batch, num_graphs)
         ctx.save_for_backward(probs, nnodes, batch)
         return out
 
@@ -759,11 +764,12 @@ def pattern_pool(x, pattern_probs, pattern_num_nodes, batch, num_graphs):
 
 class _EmbedNodeFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x_raw, cat_idx, table, out16=False):
+    def forward(ctx, x_raw, cat_idx, table, out16=False, pad_to=0):
         m = ext()
-        out = m.embed_node_fwd(x_raw, cat_idx, table, out16)
+        out = m.embed_node_fwd(x_raw, cat_idx, table, out16, pad_to)
         ctx.save_for_backward(cat_idx)
         ctx.f = x_raw.shape[1]
+        ctx.h = table.shape[1]
         ctx.rows = table.shape[0]
         return out
 
@@ -771,13 +777,18 @@ class _EmbedNodeFn(torch.autograd.Function):
     def backward(ctx, g):
         (cat_idx,) = ctx.saved_tensors
         m = ext()
+        # g is [n, f + h] or the padded [n, pad_to]: the table gradient reads
+        # its h columns in place (row stride g.shape[1], offset f)
         g = g.contiguous()
-        dx_raw = g[:, : ctx.f].contiguous()
-        if dx_raw.dtype != torch.float32:
-            dx_raw = dx_raw.float()
-        h = g.shape[1] - ctx.f
-        dtable = _table_grad(m, g, cat_idx, ctx.rows, h, ctx.f)
-        return dx_raw, None, dtable, None
+        dx_raw = None
+        if ctx.needs_input_grad[0]:
+            dx_raw = g[:, : ctx.f].contiguous()
+            if dx_raw.dtype != torch.float32:
+                dx_raw = dx_raw.float()
+        dtable = None
+        if ctx.needs_input_grad[2]:
+            dtable = _table_grad(m, g, cat_idx, ctx.rows, ctx.h, ctx.f)
+        return dx_raw, None, dtable, None, None
 
 
 class _EmbedEdgeFn(torch.autograd.Function):
@@ -800,13 +811,23 @@ class _EmbedEdgeFn(torch.autograd.Function):
         return None, d_ifc, d_rpc
 
 
-def embed_concat_node(x_raw, cat_X, tables, out16=False):
+def embed_concat_node(x_raw, cat_X, tables, out16=False, pad_to=None):
     """``out16`` emits the concat bf16 so layer 1's QKVS GEMM takes the
     bf16-A path — numerically identical to the fp32 tensor (the GEMM staging
-    rounds operands to bf16 either way)."""
+    rounds operands to bf16 either way).  ``pad_to`` (None = no padding)
+    widens the rows to that many columns, +0 past the concat: the first
+    conv's ``k_padded``, so that its GEMM operand is written once, already
+    padded, and the gradient that comes back is read in place."""
     if len(tables) == 1 and use_hip(x_raw):
-        return _EmbedNodeFn.apply(x_raw, cat_X[:, 0].contiguous(), tables[0], out16)
-    return ref.embed_concat_node(x_raw, cat_X, tables)
+        return _EmbedNodeFn.apply(x_raw, cat_X[:, 0].contiguous(), tables[0],
+                                  out16, 0 if pad_to is None else int(pad_to))
+    out = ref.embed_concat_node(x_raw, cat_X, tables)
+    if pad_to is not None:
+        if pad_to < out.shape[1]:
+            raise ValueError(f"pad_to={pad_to} is below the concat width "
+                             f"{out.shape[1]}")
+        out = torch.nn.functional.pad(out, (0, pad_to - out.shape[1]))
+    return out
 
 
 def embed_concat_edge(edge_attr, interface_table, rpctype_table):
@@ -1038,6 +1059,82 @@ def edge_attention_fused_bn_relu(qkvs, pifc, prpc, edge_attr, csr, gamma,
         edge_attr, row_ptr, csr_src, col_ptr, csc_dst, csc_eid, heads,
         running_mean, running_var, momentum, eps, comm, dropout_p, sinks,
         _sink_anchor(qkvs.device))
+
+
+def pool_attn_fuse_enabled(h: int) -> bool:
+    """The last conv's attention backward forms the pattern pool's gradient
+    itself (bf16 ``qkvs`` on the GPU, h in {256, 512}: the widths of the
+    act16 attention kernels that carry the mode).
+    PERTGNN_NO_POOL_ATTN_FUSE=1 keeps the two separate Functions; read per
+    call so one process can run both."""
+    import os
+    return (h in (256, 512)
+            and os.environ.get("PERTGNN_NO_POOL_ATTN_FUSE", "0") != "1")
+
+
+class _AttnPoolFn(torch.autograd.Function):
+    """Fused attention forward (fp32 out) -> pattern pool forward, returning
+    both.  The forward is the two existing ops.  When only the pooled output
+    carries a gradient (the training loss reads ``global_predict`` alone) the
+    attention backward forms each node's gradient ``gmean[batch[i]] *
+    probs[i] / nnodes[i]`` itself — the fp32 [N, H] tensor that
+    ``seg_pool_bwd`` writes and both attention kernels read back never
+    exists.  A gradient on ``x`` takes the two existing backward ops."""
+
+    @staticmethod
+    def forward(ctx, qkvs, pifc, prpc, edge_attr, row_ptr, csr_src, col_ptr,
+                csc_dst, csc_eid, heads, probs, nnodes, batch, num_graphs):
+        m = ext()
+        ctx.set_materialize_grads(False)
+        x, alpha = m.edge_attn_fused_fwd(qkvs, pifc, prpc, edge_attr, row_ptr,
+                                         csr_src, False, heads)
+        probs = probs.contiguous()
+        nnodes = nnodes.contiguous()
+        mean_x = _pool_forward(m, x, probs, nnodes, batch, num_graphs)
+        ctx.save_for_backward(qkvs, pifc, prpc, edge_attr, alpha, row_ptr,
+                              csr_src, col_ptr, csc_dst, csc_eid, probs,
+                              nnodes, batch)
+        ctx.heads = heads
+        return x, mean_x
+
+    @staticmethod
+    def backward(ctx, gx, gmean):
+        (qkvs, pifc, prpc, edge_attr, alpha, row_ptr, csr_src, col_ptr,
+         csc_dst, csc_eid, probs, nnodes, batch) = ctx.saved_tensors
+        none = (None,) * 11
+        if gx is None and gmean is None:
+            return (None, None, None) + none
+        m = ext()
+        attn = (qkvs, pifc, prpc, edge_attr, alpha, row_ptr, csr_src,
+                col_ptr, csc_dst, csc_eid, ctx.heads)
+        if gx is None:
+            dqkvs, de = m.edge_attn_pool_bwd16(gmean.contiguous(), probs,
+                                               nnodes, batch, *attn)
+        else:
+            g = gx.contiguous()
+            if gmean is not None:
+                g = m.seg_pool_bwd(gmean.contiguous(), probs, nnodes,
+                                   batch) + g
+            dqkvs, de = m.edge_attn_fused_bwd(g, *attn)
+        dpifc, dprpc = _attn_table_grads(m, de, pifc, prpc, edge_attr)
+        return (dqkvs, dpifc, dprpc) + none
+
+
+def edge_attention_fused_pool(qkvs, pifc, prpc, edge_attr, csr, probs,
+                              nnodes, batch, num_graphs, heads=1):
+    """``x = edge_attention_fused(...)`` (fp32 out) and ``pattern_pool(x,
+    ...)`` -> ``(x, mean_x)``: one autograd node where
+    ``pool_attn_fuse_enabled`` holds for bf16 ``qkvs`` on the GPU, the two
+    separate ops everywhere else.  Same forward ops, same results."""
+    h = qkvs.shape[1] // 4
+    if (use_hip(qkvs) and qkvs.dtype == torch.bfloat16
+            and pool_attn_fuse_enabled(h)):
+        row_ptr, csr_src, col_ptr, csc_dst, csc_eid = csr
+        return _AttnPoolFn.apply(qkvs, pifc, prpc, edge_attr, row_ptr,
+                                 csr_src, col_ptr, csc_dst, csc_eid, heads,
+                                 probs, nnodes, batch, num_graphs)
+    x = edge_attention_fused(qkvs, pifc, prpc, edge_attr, csr, heads=heads)
+    return x, pattern_pool(x, probs, nnodes, batch, num_graphs)
 
 
 class _EagerSyncBNFn(torch.autograd.Function):
