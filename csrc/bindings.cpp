@@ -217,6 +217,10 @@ void launch_embed_grouped_scatter_bal(const void*, int, const int*,
                                       hipStream_t);
 void launch_rows_sum_lists(const void*, int, const int*, const int*, void*, int,
                            int, int, int, hipStream_t);
+void launch_rows_sum_lists_wide(const void*, int, int, const int*, const int*,
+                                float*, int, int, int, int, int, hipStream_t);
+void launch_embed_fold_gemm(const float*, const float*, float*, int, int, int,
+                            int, int, bool, hipStream_t);
 void launch_vocab_scatter(const float*, const long*, long, float*, long, int,
                           int, int, int, hipStream_t);
 void launch_vocab_scatter_dual(const float*, const long*, int, float*, float*,
@@ -873,6 +877,73 @@ torch::Tensor edge_table_grad(torch::Tensor de, torch::Tensor idx1,
   launch_rows_sum_lists(partial.data_ptr(), 0, idx3.data_ptr<int>(),
                         lptr3.data_ptr<int>(), out.data_ptr(), out16,
                         (int)(V + R), h, (int)unroll, s);
+  return out;
+}
+
+// The category-table gradient of the first layer without its dgrad GEMM:
+// dtable[rows, h] = G . B, where G[c, :] is the sum of the dqkvs rows
+// [n, 4h] (bf16) of category c and B[j, t] = bf16(w4[j, f + t]) are the
+// table's columns of the layer's fp32 weight [4h, k_padded], rounded as the
+// dgrad GEMM rounds them.  The six plan tensors (cat_table_plan in
+// pertgnn/ops/functional.py, one key) drive three launches of the wide list
+// sum (two without a level 2) over all 4h columns, fp32 in list order; the
+// small fp32 GEMM then stores dtable, or adds it into `sink` and returns an
+// empty tensor.  No [n, .] intermediate, no memset, no atomics.  n == 0:
+// zeros (the sink untouched), nothing launched.
+torch::Tensor embed_dgrad_fold(torch::Tensor dqkvs, torch::Tensor idx1,
+                               torch::Tensor lptr1, torch::Tensor idx2,
+                               torch::Tensor lptr2, torch::Tensor idx3,
+                               torch::Tensor lptr3, torch::Tensor w4,
+                               int64_t f, int64_t h, int64_t rows,
+                               OptTensor sink = std::nullopt,
+                               int64_t unroll = 8, int64_t seg_cols = 256) {
+  CHECK_IN(dqkvs); CHECK_IN(idx1); CHECK_IN(lptr1); CHECK_IN(idx2);
+  CHECK_IN(lptr2); CHECK_IN(idx3); CHECK_IN(lptr3); CHECK_IN(w4);
+  TORCH_CHECK(h == 256 || h == 512, "embed_dgrad_fold: h must be 256 or 512");
+  TORCH_CHECK(dqkvs.dim() == 2 && dqkvs.size(1) == 4 * h &&
+                  dqkvs.scalar_type() == torch::kBFloat16,
+              "embed_dgrad_fold: dqkvs must be bf16 [n, 4h]");
+  TORCH_CHECK(w4.dim() == 2 && w4.size(0) == 4 * h &&
+                  w4.scalar_type() == torch::kFloat32,
+              "embed_dgrad_fold: w4 must be fp32 [4h, k_padded]");
+  TORCH_CHECK(f >= 0 && f + h <= w4.size(1),
+              "embed_dgrad_fold: columns f..f+h must lie inside w4");
+  for (const auto& t : {idx1, lptr1, idx2, lptr2, idx3, lptr3})
+    TORCH_CHECK(t.scalar_type() == torch::kInt32 && t.dim() == 1,
+                "plan tensors must be 1-D int32");
+  TORCH_CHECK(rows >= 0 && lptr3.numel() == rows + 1,
+              "embed_dgrad_fold: lptr3 must have rows+1 entries");
+  TORCH_CHECK(lptr1.numel() >= 1 && lptr2.numel() >= 1,
+              "lptr1/lptr2 must have at least one entry");
+  TORCH_CHECK(idx1.numel() == dqkvs.size(0),
+              "level 1 must list every row of dqkvs exactly once");
+  float* sink_p = grad_sink(sink, dqkvs, {rows, h}, "embed_dgrad_fold");
+  auto fopt = dqkvs.options().dtype(torch::kFloat32);
+  if (dqkvs.size(0) == 0 || rows == 0)
+    return sink_p ? torch::empty({0}, fopt) : torch::zeros({rows, h}, fopt);
+  const int width = (int)(4 * h);
+  const long n1 = lptr1.numel() - 1;
+  const long n2 = lptr2.numel() - 1;
+  // level-1 rows, level-2 rows, then G
+  auto buf = torch::empty({n1 + n2 + rows, (long)width}, fopt);
+  float* p = buf.data_ptr<float>();
+  float* G = p + (n1 + n2) * width;
+  hipStream_t s = cur_stream();
+  launch_rows_sum_lists_wide(dqkvs.data_ptr(), 1, width, idx1.data_ptr<int>(),
+                             lptr1.data_ptr<int>(), p, width, (int)n1, width,
+                             (int)seg_cols, (int)unroll, s);
+  if (n2 > 0)
+    launch_rows_sum_lists_wide(p, 0, width, idx2.data_ptr<int>(),
+                               lptr2.data_ptr<int>(), p + n1 * width, width,
+                               (int)n2, width, (int)seg_cols, (int)unroll, s);
+  launch_rows_sum_lists_wide(p, 0, width, idx3.data_ptr<int>(),
+                             lptr3.data_ptr<int>(), G, width, (int)rows, width,
+                             (int)seg_cols, (int)unroll, s);
+  auto out = torch::empty({sink_p ? 0 : rows, sink_p ? 0 : h}, fopt);
+  launch_embed_fold_gemm(G, w4.data_ptr<float>(),
+                         sink_p ? sink_p : out.data_ptr<float>(), (int)rows,
+                         width, (int)h, (int)w4.size(1), (int)f,
+                         sink_p != nullptr, s);
   return out;
 }
 
@@ -2137,6 +2208,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("lptr1"), py::arg("idx2"), py::arg("lptr2"),
           py::arg("idx3"), py::arg("lptr3"), py::arg("V"), py::arg("R"),
           py::arg("out_dtype"), py::arg("unroll") = 8);
+  mod.def("embed_dgrad_fold", &embed_dgrad_fold, py::arg("dqkvs"),
+          py::arg("idx1"), py::arg("lptr1"), py::arg("idx2"), py::arg("lptr2"),
+          py::arg("idx3"), py::arg("lptr3"), py::arg("w4"), py::arg("f"),
+          py::arg("h"), py::arg("rows"), py::arg("sink") = py::none(),
+          py::arg("unroll") = 8, py::arg("seg_cols") = 256);
   mod.def("bn_stats", &bn_stats);
   mod.def("bn_finalize_apply", &bn_finalize_apply, py::arg("x"),
           py::arg("partials"), py::arg("gamma"), py::arg("beta"),

@@ -412,3 +412,114 @@ void launch_colsum(const float* g, float* out, long m, int n, hipStream_t s) {
   colsum_par_kernel<<<dim3(blocks), dim3(256), n * sizeof(float), s>>>(g, out,
                                                                        m, n);
 }
+
+// ---------------------------------------------------------------------------
+// Small table GEMM of the folded layer-1 dgrad (embed_dgrad_fold in
+// bindings.cpp): out[rows, h] (+)= G[rows, K] . B with
+// B[j, c] = (float)(__bf16)w[j * ldw + col0 + c], the bf16-rounded weight
+// columns the bf16 dgrad GEMM multiplies by, read in place from the fp32
+// parameter (4-byte aligned only, so scalar loads).  G stays fp32: plain
+// fmaf chains over k = 0..K-1 in order, one owner per output element, so
+// the result is bitwise reproducible.  A 32x64 output tile per block, a
+// 2x4 micro-tile per thread.  The K loop is bound by load latency, not by
+// FMAs (rows is about 1k: some 130 blocks for 256 CUs), so a step is
+// BK = 128 deep: 36 loads per thread in flight at once, the next step's
+// issued before the current step's FMAs (one LDS buffer, two barriers per
+// step).  BK = 32 measured 70 us at rows = 1030, K = 1024, h = 256.
+// Needs K % 128 == 0 and h % 64 == 0; rows are guarded.
+// ---------------------------------------------------------------------------
+#define EDF_BM 32
+#define EDF_BN 64
+#define EDF_BK 128
+
+template <bool ACC>
+__global__ __launch_bounds__(256) void embed_fold_gemm_kernel(
+    const float* __restrict__ G, const float* __restrict__ w,
+    float* __restrict__ out, int rows, int K, int h, int ldw, int col0) {
+  __shared__ float gs[EDF_BK][EDF_BM + 4];
+  __shared__ float bs[EDF_BK][EDF_BN];
+  const int t = threadIdx.x;
+  const int c0 = blockIdx.x * EDF_BN;
+  const int r0 = blockIdx.y * EDF_BM;
+  // staging roles: G row g_row, k quads g_kq + 32 i; B column b_c, rows
+  // b_k + 4 i
+  const int g_row = t / 8, g_kq = (t % 8) * 4;
+  const bool g_ok = r0 + g_row < rows;
+  const float* g_src = G + (long)(r0 + g_row) * K + g_kq;
+  const int b_c = t % EDF_BN, b_k = t / EDF_BN;
+  const float* b_src = w + (long)b_k * ldw + col0 + c0 + b_c;
+  // compute roles
+  const int tx = t % 16, ty = t / 16;
+
+  f32x4 g_reg[EDF_BK / 32];
+  float b_reg[EDF_BK / 4];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < EDF_BK / 32; ++i)
+      g_reg[i] = g_ok ? *reinterpret_cast<const f32x4*>(g_src + k0 + 32 * i)
+                      : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < EDF_BK / 4; ++i)
+      b_reg[i] = (float)(__bf16)b_src[(long)(k0 + 4 * i) * ldw];
+  };
+  auto store = [&]() {
+#pragma unroll
+    for (int i = 0; i < EDF_BK / 32; ++i)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) gs[g_kq + 32 * i + u][g_row] = g_reg[i][u];
+#pragma unroll
+    for (int i = 0; i < EDF_BK / 4; ++i) bs[b_k + 4 * i][b_c] = b_reg[i];
+  };
+
+  float acc[2][4];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
+
+  const int nk = K / EDF_BK;
+  load(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    store();
+    __syncthreads();
+    if (kt + 1 < nk) load((kt + 1) * EDF_BK);
+#pragma unroll 8
+    for (int k = 0; k < EDF_BK; ++k) {
+      const float a0 = gs[k][ty * 2];
+      const float a1 = gs[k][ty * 2 + 1];
+      const f32x4 b = *reinterpret_cast<const f32x4*>(&bs[k][tx * 4]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[0][j] = __builtin_fmaf(a0, b[j], acc[0][j]);
+        acc[1][j] = __builtin_fmaf(a1, b[j], acc[1][j]);
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = r0 + ty * 2 + i;
+    if (r >= rows) continue;
+    float* o = out + (long)r * h + c0 + tx * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = ACC ? o[j] + acc[i][j] : acc[i][j];
+  }
+}
+
+// accumulate: out is a gradient sink slice (+=), else a plain store
+void launch_embed_fold_gemm(const float* G, const float* w, float* out,
+                            int rows, int K, int h, int ldw, int col0,
+                            bool accumulate, hipStream_t s) {
+  if (rows == 0) return;
+  if (K <= 0 || K % EDF_BK != 0) pertgnn_shape_fail("embed_fold_gemm", "K", K);
+  if (h <= 0 || h % EDF_BN != 0) pertgnn_shape_fail("embed_fold_gemm", "h", h);
+  if (col0 < 0 || col0 + h > ldw)
+    pertgnn_shape_fail("embed_fold_gemm", "col0+h", (long)col0 + h);
+  const dim3 grid(h / EDF_BN, ceil_div(rows, EDF_BM));
+  if (accumulate)
+    embed_fold_gemm_kernel<true><<<grid, dim3(256), 0, s>>>(G, w, out, rows, K,
+                                                            h, ldw, col0);
+  else
+    embed_fold_gemm_kernel<false><<<grid, dim3(256), 0, s>>>(G, w, out, rows,
+                                                             K, h, ldw, col0);
+}

@@ -488,13 +488,18 @@ __device__ __forceinline__ void rows_sum_load(const T* __restrict__ row,
   }
 }
 
+// The body serves two kernels.  rows_sum_lists_kernel sums whole rows of
+// width H = VPT*64 (both strides H, column 0).  rows_sum_lists_wide_kernel
+// sums rows wider than one wave's H columns: blockIdx.y names a column
+// segment of H columns, rows are src_stride / out_stride elements apart, so
+// a list still gets one wave per H columns (the layer-1 dqkvs [N, 4h] is
+// summed by category this way: embed_dgrad_fold in bindings.cpp).
 template <int VPT, typename TIn, typename TOut, int U>
-__global__ void rows_sum_lists_kernel(const TIn* __restrict__ src,
-                                      const int* __restrict__ idx,
-                                      const int* __restrict__ lptr,
-                                      TOut* __restrict__ out, int n_lists) {
+__device__ __forceinline__ void rows_sum_lists_body(
+    const TIn* __restrict__ src, const int* __restrict__ idx,
+    const int* __restrict__ lptr, TOut* __restrict__ out, int n_lists,
+    long src_stride, long out_stride) {
   static_assert(VPT % 4 == 0, "packed loads need 4 columns per lane");
-  constexpr int H = VPT * PERTGNN_WAVE;
   const int lane = threadIdx.x % PERTGNN_WAVE;
   const int w = __builtin_amdgcn_readfirstlane(
       blockIdx.x * WAVES_PER_BLOCK + threadIdx.x / PERTGNN_WAVE);
@@ -512,7 +517,7 @@ __global__ void rows_sum_lists_kernel(const TIn* __restrict__ src,
     float v[U][VPT];
 #pragma unroll
     for (int u = 0; u < U; ++u)
-      rows_sum_load<VPT>(src + (long)r[u] * H, lane, v[u]);
+      rows_sum_load<VPT>(src + (long)r[u] * src_stride, lane, v[u]);
 #pragma unroll
     for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -525,7 +530,7 @@ __global__ void rows_sum_lists_kernel(const TIn* __restrict__ src,
     float v[U][VPT];
 #pragma unroll
     for (int u = 0; u < U; ++u)
-      rows_sum_load<VPT>(src + (long)r[u] * H, lane, v[u]);
+      rows_sum_load<VPT>(src + (long)r[u] * src_stride, lane, v[u]);
 #pragma unroll
     for (int u = 0; u < U; ++u)
       if (p + u < p1) {
@@ -533,7 +538,7 @@ __global__ void rows_sum_lists_kernel(const TIn* __restrict__ src,
         for (int j = 0; j < VPT; ++j) acc[j] += v[u][j];
       }
   }
-  TOut* dst = out + (long)w * H + lane * VPT;
+  TOut* dst = out + (long)w * out_stride + lane * VPT;
   if constexpr (sizeof(TOut) == 2) {
 #pragma unroll
     for (int q = 0; q < VPT; q += 4) {
@@ -551,6 +556,27 @@ __global__ void rows_sum_lists_kernel(const TIn* __restrict__ src,
       *reinterpret_cast<segf4*>((float*)dst + q) = o;
     }
   }
+}
+
+template <int VPT, typename TIn, typename TOut, int U>
+__global__ void rows_sum_lists_kernel(const TIn* __restrict__ src,
+                                      const int* __restrict__ idx,
+                                      const int* __restrict__ lptr,
+                                      TOut* __restrict__ out, int n_lists) {
+  constexpr int H = VPT * PERTGNN_WAVE;
+  rows_sum_lists_body<VPT, TIn, TOut, U>(src, idx, lptr, out, n_lists, H, H);
+}
+
+template <int VPT, typename TIn, int U>
+__global__ void rows_sum_lists_wide_kernel(const TIn* __restrict__ src,
+                                           const int* __restrict__ idx,
+                                           const int* __restrict__ lptr,
+                                           float* __restrict__ out,
+                                           int n_lists, int src_stride,
+                                           int out_stride) {
+  const int col0 = blockIdx.y * (VPT * PERTGNN_WAVE);
+  rows_sum_lists_body<VPT, TIn, float, U>(src + col0, idx, lptr, out + col0,
+                                          n_lists, src_stride, out_stride);
 }
 
 // in16/out16: bf16 rows in / out (else fp32); h in {256, 512}; unroll in
@@ -582,6 +608,45 @@ void launch_rows_sum_lists(const void* src, int in16, const int* idx,
   }
 #undef RSL_T
 #undef RSL
+}
+
+// Wide form: rows of `width` columns (a multiple of seg_cols, 256 or 512),
+// one wave per list and column segment; src rows are src_stride elements
+// apart (bf16 if in16, else fp32), out rows out_stride fp32 elements.  Both
+// strides and both base pointers keep every segment 16-byte aligned for fp32
+// and 8-byte aligned for bf16 (strides % 4 == 0; checked by the binding).
+void launch_rows_sum_lists_wide(const void* src, int in16, int src_stride,
+                                const int* idx, const int* lptr, float* out,
+                                int out_stride, int n_lists, int width,
+                                int seg_cols, int unroll, hipStream_t s) {
+  if (n_lists == 0) return;
+  if (seg_cols != 256 && seg_cols != 512)
+    pertgnn_shape_fail("rows_sum_lists_wide", "seg_cols", seg_cols);
+  if (width <= 0 || width % seg_cols != 0)
+    pertgnn_shape_fail("rows_sum_lists_wide", "width", width);
+  if (src_stride < width || out_stride < width || src_stride % 4 != 0 ||
+      out_stride % 4 != 0)
+    pertgnn_shape_fail("rows_sum_lists_wide", "stride",
+                       src_stride < out_stride ? src_stride : out_stride);
+  if (unroll != 4 && unroll != 8)
+    pertgnn_shape_fail("rows_sum_lists_wide", "unroll", unroll);
+  const dim3 block(WAVES_PER_BLOCK * PERTGNN_WAVE);
+  const dim3 grid(ceil_div(n_lists, WAVES_PER_BLOCK), width / seg_cols);
+#define RSW(V, TI, UU)                                                         \
+  rows_sum_lists_wide_kernel<V, TI, UU><<<grid, block, 0, s>>>(                \
+      (const TI*)src, idx, lptr, out, n_lists, src_stride, out_stride)
+#define RSW_T(V, UU)                                                           \
+  do {                                                                         \
+    if (in16) RSW(V, __bf16, UU);                                              \
+    else RSW(V, float, UU);                                                    \
+  } while (0)
+  if (seg_cols == 256) {
+    if (unroll == 8) RSW_T(4, 8); else RSW_T(4, 4);
+  } else {
+    if (unroll == 8) RSW_T(8, 8); else RSW_T(8, 4);
+  }
+#undef RSW_T
+#undef RSW
 }
 
 // Single-pass vocab accumulator for small vocabularies: blocks stream

@@ -262,7 +262,10 @@ class TransformerConv(nn.Module):
         act16 = (ops.gemm_precision() in ("bf16", "fp16") and h % 256 == 0
                  and ops.act16_enabled())
         if act16:
-            qkvs = ops.linear16(x, self.w4, self.b4)
+            # the first conv's x is the embed concat: where its only
+            # gradient would be the category table's, that one is formed
+            # from dqkvs directly and no dgrad runs (linear16 otherwise)
+            qkvs = ops.linear16_embed(x, self.w4, self.b4)
             if pifc is not None and prpc is not None:
                 pass  # grouped: computed once for all layers by the caller
             elif ops.p16_enabled():

@@ -318,6 +318,70 @@ def edge_table_plan(edge_attr: torch.Tensor, V: int, R: int,
     return plan
 
 
+def _build_cat_table_plan(idx, rows: int, C: int):
+    """Single-key plan on a CPU int64 index vector: the ``EdgeTablePlan``
+    levels for ``rows`` outputs keyed by ``idx`` alone (V = rows, R = 0)."""
+    n = idx.numel()
+    if n and (int(idx.min()) < 0 or int(idx.max()) >= rows):
+        raise IndexError("category index outside the embedding table")
+    order = torch.argsort(idx, stable=True)
+    counts = torch.bincount(idx, minlength=rows)
+    # level 1: chunks of one category, ascending by category
+    out_of_member, lptr1 = _chunk_segments(counts, C)
+    n1 = out_of_member.numel()
+    members = torch.arange(n1)
+    cnt = (counts + C - 1) // C
+    big = cnt > C
+    in_big = big[out_of_member]
+    idx2 = members[in_big]
+    _, lptr2 = _chunk_segments(cnt[big], C)
+    n2 = lptr2.numel() - 1
+    len3 = torch.where(big, (cnt + C - 1) // C, cnt)
+    lptr3 = torch.cat([torch.zeros(1, dtype=torch.long), len3.cumsum(0)])
+    from_l2 = big[torch.repeat_interleave(torch.arange(rows), len3)]
+    idx3 = torch.empty(int(len3.sum()), dtype=torch.long)
+    idx3[from_l2] = n1 + torch.arange(n2)
+    idx3[~from_l2] = members[~in_big]
+    # what the kernels rely on (they do not bounds-check)
+    assert order.numel() == n and int(lptr1[-1]) == n
+    assert int(lptr2[-1]) == idx2.numel() and int(lptr3[-1]) == idx3.numel()
+    assert idx2.numel() == 0 or int(idx2.max()) < n1
+    assert idx3.numel() == 0 or int(idx3.max()) < n1 + n2
+    assert max(n, n1 + n2, idx3.numel(), idx2.numel()) < 2 ** 31
+    i32 = lambda t: t.to(torch.int32)
+    return EdgeTablePlan(i32(order), i32(lptr1), i32(idx2), i32(lptr2),
+                         i32(idx3), i32(lptr3), n1, n2, rows, 0, C)
+
+
+def cat_table_plan(cat_idx: torch.Tensor, rows: int,
+                   C: int | None = None) -> EdgeTablePlan:
+    """Plan for ``embed_dgrad_fold`` over the category index of every node
+    (< rows); ``C`` defaults to ``_scatter_iters()``.  Built on the host
+    (validates the indices, syncs once) and cached like ``edge_table_plan``:
+    keyed on the index view, in the same LRU byte budget, so a hit neither
+    syncs nor launches."""
+    if C is None:
+        C = _scatter_iters()
+    key = ("cat_table", cat_idx.data_ptr(), cat_idx.numel(),
+           tuple(cat_idx.stride()), rows, C)
+    hit = _GROUP_CACHE.get(key)
+    if hit is not None:
+        _GROUP_CACHE.move_to_end(key)
+        return hit[1]
+    plan = _build_cat_table_plan(cat_idx.cpu().long().contiguous(), rows, C)
+    dev = cat_idx.device
+    plan = plan._replace(**{f: getattr(plan, f).to(dev) for f in
+                            ("idx1", "lptr1", "idx2", "lptr2", "idx3",
+                             "lptr3")})
+    nbytes = sum(t.numel() for t in plan.tensors()) * 4
+    while _GROUP_CACHE and _GROUP_CACHE_BYTES[0] + nbytes > _GROUP_CACHE_CAP:
+        _, old = _GROUP_CACHE.popitem(last=False)
+        _GROUP_CACHE_BYTES[0] -= old[-1]
+    _GROUP_CACHE[key] = (cat_idx, plan, nbytes)
+    _GROUP_CACHE_BYTES[0] += nbytes
+    return plan
+
+
 def apply_plan_reference(plan: EdgeTablePlan, de: torch.Tensor):
     """The three passes of ``edge_table_grad`` with plain torch indexing
     (fp32 accumulation, fp64 for fp64 input): returns (dP_ifc [V, h],
@@ -502,6 +566,94 @@ def linear16(x, w, b=None):
         return _Linear16Fn.apply(x, w, b)
     return _Linear16Fn.apply(x, _sunk(w, w_sink), _sunk(b, b_sink), w_sink,
                              b_sink, _sink_anchor(x.device))
+
+
+def embed_dgrad_fold_enabled() -> bool:
+    """Layer-1 dgrad folded into the category-table gradient
+    (PERTGNN_NO_EMBED_DGRAD_FOLD=1 keeps the dgrad GEMM and the grouped
+    scatter over its output; read per call so one process can run both)."""
+    import os
+    return os.environ.get("PERTGNN_NO_EMBED_DGRAD_FOLD", "0") != "1"
+
+
+class EmbedSource(NamedTuple):
+    """What produced an ``embed_concat_node`` output (recorded on it as
+    ``_embed_src``): columns ``f .. f+h`` of row i are ``table[cat_idx[i]]``,
+    the first ``f`` are ``x_raw``, the rest +0."""
+    cat_idx: torch.Tensor
+    table: torch.Tensor
+    f: int
+    h: int
+    x_raw_requires_grad: bool
+
+
+class _Linear16EmbedFn(torch.autograd.Function):
+    """``linear16`` of the first layer when the only gradient its operand
+    ``x`` = [x_raw | table[cat_idx] | 0] would carry is the category table's:
+    the table is a direct input and x comes in detached.  With G[c] the sum
+    of the dqkvs rows of category c,  dtable = G . bf16(w)[:, f:f+h]
+    (``embed_dgrad_fold``): the [N, k_padded] dgrad GEMM, its output and the
+    strided gather over it never run, and the dqkvs rows are summed in fp32
+    before the one multiplication instead of being rounded to bf16 per node.
+    dw and db are ``linear_wgrad16_b16``'s, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, table, cat_idx, f, w_sink, b_sink, t_sink,
+                anchor):
+        m = ext()
+        bb = b if b is not None else torch.empty(0, dtype=torch.float32, device=x.device)
+        ctx.w_sink, ctx.b_sink, ctx.t_sink = w_sink, b_sink, t_sink
+        # no transposed weight image: nothing runs a dgrad
+        y = m.linear_fwd_a16o16(x, w, bb, False)
+        ctx.save_for_backward(x, w, cat_idx)
+        ctx.has_bias = b is not None
+        ctx.f, ctx.rows, ctx.h = f, table.shape[0], table.shape[1]
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, cat_idx = ctx.saved_tensors
+        m = ext()
+        g = g.contiguous()
+        dw, db = m.linear_wgrad16_b16(g, x, ctx.has_bias, False, ctx.w_sink,
+                                      ctx.b_sink)
+        dtable = None
+        if ctx.t_sink is not None or ctx.needs_input_grad[3]:
+            plan = cat_table_plan(cat_idx, ctx.rows)
+            dtable = m.embed_dgrad_fold(g, *plan.tensors(), w, ctx.f, ctx.h,
+                                        ctx.rows, ctx.t_sink)
+            if ctx.t_sink is not None:
+                dtable = None
+        if ctx.w_sink is not None:  # dw and db are in the sinks
+            dw = db = None
+        return (None, dw, (db if ctx.has_bias else None), dtable, None, None,
+                None, None, None, None)
+
+
+def linear16_embed(x, w, b=None):
+    """``linear16(x, w, b)`` for an ``x`` that ``embed_concat_node`` wrote:
+    where the eligibility conditions hold (bf16 operand and bf16 matrix
+    cores, one category table that requires grad, no gradient wanted for
+    ``x_raw``, h in {256, 512}, the switch on) the fold node above replaces
+    ``linear16``; anything else is ``linear16`` unchanged."""
+    src = getattr(x, "_embed_src", None)
+    if (src is None or not embed_dgrad_fold_enabled()
+            or not torch.is_grad_enabled()
+            or x.dtype != torch.bfloat16 or gemm_precision() != "bf16"
+            or src.x_raw_requires_grad or src.h not in (256, 512)
+            or not src.table.requires_grad or not x.requires_grad
+            or w.shape[0] != 4 * src.h or src.f + src.h > w.shape[1]
+            or x.shape[1] != w.shape[1]):
+        return linear16(x, w, b)
+    w_sink = grad_sink(w)
+    b_sink = grad_sink(b) if b is not None else None
+    if w_sink is None or (b is not None and b_sink is None):
+        w_sink = b_sink = None
+    t_sink = grad_sink(src.table)
+    return _Linear16EmbedFn.apply(
+        x.detach(), _sunk(w, w_sink), _sunk(b, b_sink),
+        _sunk(src.table, t_sink), src.cat_idx, src.f, w_sink, b_sink, t_sink,
+        _sink_anchor(x.device))
 
 
 class _PTablesFn(torch.autograd.Function):
@@ -819,8 +971,14 @@ def embed_concat_node(x_raw, cat_X, tables, out16=False, pad_to=None):
     conv's ``k_padded``, so that its GEMM operand is written once, already
     padded, and the gradient that comes back is read in place."""
     if len(tables) == 1 and use_hip(x_raw):
-        return _EmbedNodeFn.apply(x_raw, cat_X[:, 0].contiguous(), tables[0],
-                                  out16, 0 if pad_to is None else int(pad_to))
+        cat_idx = cat_X[:, 0]
+        out = _EmbedNodeFn.apply(x_raw, cat_idx.contiguous(), tables[0],
+                                 out16, 0 if pad_to is None else int(pad_to))
+        # what produced it, for the first conv (linear16_embed); the index
+        # VIEW is recorded: it is what stays the same from step to step
+        out._embed_src = EmbedSource(cat_idx, tables[0], x_raw.shape[1],
+                                     tables[0].shape[1], x_raw.requires_grad)
+        return out
     out = ref.embed_concat_node(x_raw, cat_X, tables)
     if pad_to is not None:
         if pad_to < out.shape[1]:
