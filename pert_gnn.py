@@ -21,8 +21,19 @@ from pertgnn.models import SAGEDeterministic
 from pertgnn.parallel import Comm
 from pertgnn.train.optim import FlatGradAllReduce, FusedAdam
 from pertgnn.train import evaluate, load_checkpoint, save_checkpoint, train_epoch
-from pertgnn.train.checkpoint import check_heads
+from pertgnn.train.checkpoint import check_heads, check_taus
 from pertgnn.utils import JsonlLogger
+
+
+def parse_taus(text):
+    """``--taus`` value: comma-separated, 1..8 strictly increasing levels
+    in (0, 1)."""
+    from pertgnn.ops.reference import check_taus as check_levels
+
+    try:
+        return check_levels([float(t) for t in text.split(",")])
+    except ValueError as exc:
+        raise argparse.ArgumentTypeError(str(exc)) from None
 
 
 def build_parser():
@@ -35,7 +46,9 @@ def build_parser():
     parser.add_argument("--hidden_channels", type=int, default=32)
     parser.add_argument("--dropout", type=float, default=0)
     parser.add_argument("--lr", type=float, default=0.0003)
-    parser.add_argument("--tau", type=float, default=0.5,
+    # default None = "not given" (resolved to the reference's 0.5 by
+    # resolve_levels), so --taus can tell an explicit --tau apart
+    parser.add_argument("--tau", type=float, default=None,
                         help="the quantile level, real number between 0 and 1, 0.5 (median) by default")
     parser.add_argument("--epochs", type=int, default=100)
     parser.add_argument("--runs", type=int, default=10)            # dead (compat)
@@ -81,12 +94,41 @@ def build_parser():
                              "--hidden_channels; 1 = the reference model). "
                              "Recorded in the checkpoint: resuming or "
                              "predicting with another value is refused")
+    parser.add_argument("--taus", type=parse_taus, default=None,
+                        metavar="T1,T2,...",
+                        help="quantile levels of ONE model, e.g. 0.5,0.9,0.99 "
+                             "(1..8 strictly increasing values in (0, 1)): "
+                             "the decoder emits one column per level and "
+                             "training minimises the summed pinball loss. "
+                             "Not combinable with --tau. Recorded in the "
+                             "checkpoint: resuming or predicting with other "
+                             "levels is refused")
     parser.add_argument("--fast_eval", action="store_true",
                         help="per-epoch valid/test passes through the inference "
                              "path (pertgnn.infer.Predictor, refreshed after "
                              "every training epoch; captured once over the "
                              "resident eval batches under --hipgraph)")
     return parser
+
+
+def parse_args(argv=None):
+    """Parsed arguments with the levels resolved: ``args.tau`` is the scalar
+    level (0.5 unless given), ``args.levels`` the tuple of levels of a
+    --taus run or None, ``args.levels_given`` whether either flag was
+    passed."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.taus is not None and args.tau is not None:
+        parser.error("--taus cannot be combined with --tau: give the levels "
+                     "of a multi-level model with --taus alone")
+    args.levels_given = args.taus is not None or args.tau is not None
+    args.levels = args.taus
+    if args.levels is not None and len(args.levels) == 1:
+        # one level is the scalar run at that level
+        args.tau, args.levels = args.levels[0], None
+    if args.tau is None:
+        args.tau = 0.5
+    return args
 
 
 def run_predict(args, model, device, samples):
@@ -106,24 +148,42 @@ def run_predict(args, model, device, samples):
         mode = predictor.capture(resident)
         print(f"# predict stepping mode: {mode} "
               f"({len(resident)} resident batches)")
-    acc = torch.zeros(3, dtype=torch.float64, device=device)
+    levels, tau = args.levels, args.tau
+    nq = len(levels) if levels else 1
+    acc = torch.zeros(3 if levels is None else 3 + 2 * nq,
+                      dtype=torch.float64, device=device)
     preds = []
     n = 0
     with torch.no_grad():
         for i, b in enumerate(resident):
             pred = (predictor.replay(i) if args.hipgraph
                     else predictor.predict_batch(b))
-            sums = ops.eval_metrics(b.y, pred, args.tau)
-            for j, v in enumerate(sums):
-                acc[j] += v.double() if torch.is_tensor(v) else v
+            if levels is None:
+                sums = ops.eval_metrics(b.y, pred, tau)
+                for j, v in enumerate(sums):
+                    acc[j] += v.double() if torch.is_tensor(v) else v
+            else:
+                # the metrics of what is written out: the rearranged rows
+                acc += ops.eval_metrics(b.y, pred, levels).double()
             preds.append(pred)
             n += b.num_graphs
     out = (torch.cat(preds).cpu() if preds
-           else torch.empty(0, dtype=torch.float32))  # the one host sync
-    mae, mape, qloss = (acc / max(n, 1)).tolist()
+           else torch.empty((0,) if levels is None else (0, nq),
+                            dtype=torch.float32))  # the one host sync
     with open(args.predict, "wb") as f:
         np.save(f, out.numpy().astype(np.float32, copy=False))
-    print(f"Predict: n={n}, mae={mae!r}, mape={mape!r}, q loss={qloss!r}")
+    if levels is None:
+        mae, mape, qloss = (acc / max(n, 1)).tolist()
+        print(f"Predict: n={n}, mae={mae!r}, mape={mape!r}, q loss={qloss!r}")
+        return
+    from pertgnn.train import QuantileReport
+
+    rep = QuantileReport.from_sums(levels, acc.tolist(), n)
+    per_level = ", ".join(
+        f"tau={t!r}: q loss={q!r}, coverage={c!r}"
+        for t, q, c in zip(rep.taus, rep.qloss, rep.coverage))
+    print(f"Predict: n={n}, mae={rep.mae!r}, mape={rep.mape!r}, "
+          f"q loss={rep.qloss_total!r}, {per_level}")
 
 
 def load_artifacts(args, comm=None):
@@ -161,8 +221,12 @@ def load_artifacts(args, comm=None):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    print(args)
+    args = parse_args(argv)
+    shown = argparse.Namespace(**vars(args))
+    del shown.levels, shown.levels_given
+    if shown.taus is None:
+        del shown.taus  # a run without --taus prints the line it always did
+    print(shown)
     comm = Comm()
     torch.manual_seed(args.seed + comm.rank)
     if args.predict:
@@ -172,6 +236,17 @@ def main(argv=None):
         if not args.checkpoint or not os.path.exists(args.checkpoint):
             raise SystemExit("--predict needs an existing --checkpoint "
                              f"(got {args.checkpoint!r})")
+        # loaded once, here: the levels decide the decoder width below
+        predict_state = torch.load(args.checkpoint, map_location="cpu",
+                                   weights_only=False)
+        if not args.levels_given:
+            # the levels come from the checkpoint; one without the field
+            # means unknown: the default
+            saved = predict_state.get("taus")
+            if saved is not None and len(saved) > 1:
+                args.levels = tuple(float(t) for t in saved)
+            elif saved is not None:
+                args.tau = float(saved[0])
 
     if torch.cuda.is_available():
         # reference semantics: single process honors --device (pert_gnn.py:36);
@@ -233,7 +308,11 @@ def main(argv=None):
         num_features + 1, [unique_ms_max + 1], entry_id_max, interface_id_max,
         rpctype_id_max, args.hidden_channels, args.num_layers, args.dropout,
         heads=args.heads,
+        num_quantiles=len(args.levels) if args.levels else 1,
     ).to(device)
+    # the levels of this run: the tuple of a --taus run, else the scalar
+    run_levels = tuple(args.levels) if args.levels else (args.tau,)
+    model.taus = run_levels
     comm.broadcast_module_(model)
     if args.sync_bn and comm.distributed:
         model.enable_sync_bn(comm)
@@ -242,9 +321,10 @@ def main(argv=None):
         set_gemm_precision(args.precision)
     if args.predict:
         # model state only: no optimizer, no RNG restore
-        state = torch.load(args.checkpoint, map_location=device,
-                           weights_only=False)
+        state = predict_state  # load_state_dict copies it to the device
         check_heads(state, model, args.checkpoint)
+        check_taus(state, run_levels if args.levels_given else None,
+                   args.checkpoint)
         model.load_state_dict(state["model"])
         samples = {"test": test_list, "valid": valid_list, "train": train_list,
                    "all": train_list + valid_list + test_list}[args.predict_split]
@@ -262,9 +342,13 @@ def main(argv=None):
 
     start_epoch = 1
     if args.checkpoint and os.path.exists(args.checkpoint):
-        ep, _ = load_checkpoint(args.checkpoint, model, optimizer, map_location=device)
+        ep, _ = load_checkpoint(args.checkpoint, model, optimizer,
+                                map_location=device, taus=run_levels)
         start_epoch = ep + 1
         log.print0(f"resumed from {args.checkpoint} at epoch {ep}")
+
+    # what the loops take as ``tau``: the scalar, or the tuple of levels
+    tau_arg = args.levels if args.levels else args.tau
 
     stepper = None
     if args.hipgraph:
@@ -274,7 +358,7 @@ def main(argv=None):
             train_shard, args.batch_size, device, args.seed + comm.rank,
             collate_fn=collate_native,
         )
-        stepper = GraphStepper(model, optimizer, engine, comm, args.tau,
+        stepper = GraphStepper(model, optimizer, engine, comm, tau_arg,
                                device, resident, loss_scale=args.loss_scale,
                                seed=args.seed + comm.rank)
         mode = stepper.capture()
@@ -304,7 +388,7 @@ def main(argv=None):
     def run_train_epoch(epoch_stats):
         if stepper is None:
             return train_epoch(
-                model, train_loader, optimizer, args.tau, device, engine=engine,
+                model, train_loader, optimizer, tau_arg, device, engine=engine,
                 comm=comm, stats_out=epoch_stats, loss_scale=args.loss_scale,
             )
         t0 = _time.perf_counter()
@@ -319,6 +403,12 @@ def main(argv=None):
             "epoch_s": elapsed,
             "graphs_per_s": n / max(elapsed, 1e-9),
         })
+        if stepper.last_q_loss is not None:
+            # rank-local averages -> global: weight by this rank's graphs
+            ql = [v * stepper.n_graphs for v in stepper.last_q_loss]
+            if comm.distributed:
+                ql = [comm.all_reduce_scalar(v) for v in ql]
+            epoch_stats["q_loss"] = [v / max(n, 1) for v in ql]
         n = max(n, 1)
         return loss_sum / n, mape_sum / n
 
@@ -327,25 +417,50 @@ def main(argv=None):
         train_mae, train_mape = run_train_epoch(epoch_stats)
         if predictor is not None:
             predictor.refresh()  # the epoch above changed the weights
-        valid_mae, valid_mape, valid_q = evaluate(
-            model, valid_loader, args.tau, device, comm=comm, predictor=predictor)
-        test_mae, test_mape, test_q = evaluate(
-            model, test_loader, args.tau, device, comm=comm, predictor=predictor)
+        valid_rep = evaluate(
+            model, valid_loader, tau_arg, device, comm=comm, predictor=predictor)
+        test_rep = evaluate(
+            model, test_loader, tau_arg, device, comm=comm, predictor=predictor)
+        if args.levels:
+            # point-level MAE/MAPE and the summed pinball loss on the line
+            valid_mae, valid_mape, valid_q = (
+                valid_rep.mae, valid_rep.mape, valid_rep.qloss_total)
+            test_mae, test_mape, test_q = (
+                test_rep.mae, test_rep.mape, test_rep.qloss_total)
+        else:
+            valid_mae, valid_mape, valid_q = valid_rep
+            test_mae, test_mape, test_q = test_rep
         # reference epoch line format (pert_gnn.py:348-350)
         log.print0(
             f"Epoch: {epoch}, Train: {train_mae}, Test mae: {test_mae}, "
             f"Train mape: {train_mape}, Test mape: {test_mape}, Test q95 loss: {test_q}"
         )
-        log.log({
+        record = {
             "epoch": epoch, "train_loss": train_mae, "train_mape": train_mape,
             **epoch_stats,
             "valid_mae": valid_mae, "valid_mape": valid_mape, "valid_q": valid_q,
             "test_mae": test_mae, "test_mape": test_mape, "test_q": test_q,
-        })
+        }
+        if args.levels:
+            for t, q, c in zip(test_rep.taus, test_rep.qloss, test_rep.coverage):
+                log.print0(f"  tau={t}: test q loss={q}, coverage={c}")
+            log.print0(f"  crossing={test_rep.crossing}")
+            record.update({
+                "taus": list(args.levels),
+                "valid_q_levels": valid_rep.qloss,
+                "test_q_levels": test_rep.qloss,
+                "valid_coverage": valid_rep.coverage,
+                "test_coverage": test_rep.coverage,
+                "valid_crossing": valid_rep.crossing,
+                "test_crossing": test_rep.crossing,
+            })
+        log.log(record)
         if args.checkpoint and epoch % args.checkpoint_every == 0:
-            save_checkpoint(args.checkpoint, model, optimizer, epoch, comm=comm)
+            save_checkpoint(args.checkpoint, model, optimizer, epoch, comm=comm,
+                            taus=run_levels)
     if args.checkpoint:
-        save_checkpoint(args.checkpoint, model, optimizer, args.epochs, comm=comm)
+        save_checkpoint(args.checkpoint, model, optimizer, args.epochs, comm=comm,
+                        taus=run_levels)
     log.close()
     comm.finalize()
 

@@ -82,12 +82,25 @@ class Predictor:
         vr = model.rpctype_embeds.weight.shape[0]
         self.p_tables = [(torch.empty(vi, h, **pdt), torch.empty(vr, h, **pdt))
                          for _ in model.convs]
+        self.num_quantiles = m_q = int(model.global_linear2.weight.shape[0])
+        if not 1 <= m_q <= 8:
+            raise ValueError(f"the model emits {m_q} quantile levels; 1..8 "
+                             "are supported")
         self._graphs = None
         self._batches = None
         self._out = None
+        self._raw = None
         self._index = {}
         self.mode = "eager"
         self.refresh()
+
+    @property
+    def taus(self):
+        """The quantile levels of the model's output columns, read from
+        ``model.taus`` (set by the CLI / checkpoint loader); None if
+        unknown."""
+        t = getattr(self.model, "taus", None)
+        return tuple(t) if t is not None else None
 
     # -- weight-only caches --------------------------------------------------
     @torch.no_grad()
@@ -120,10 +133,14 @@ class Predictor:
                 "its cached P tables no longer match — build a new Predictor")
 
     @torch.no_grad()
-    def predict_batch(self, b, return_local: bool = False):
-        """Global latency prediction for one collated batch, flattened, fp32
-        ``[num_graphs]`` (with ``return_local`` also the per-node local
-        prediction ``[N,1]``).  Same embed, QKVS GEMM, pool and decoder ops
+    def predict_batch(self, b, return_local: bool = False,
+                      rearrange: bool = True):
+        """Global latency prediction for one collated batch, fp32: flattened
+        ``[num_graphs]`` for a one-level model, ``[num_graphs, Q]`` for a
+        model with Q quantile levels — with ``rearrange`` (the default)
+        every row sorted ascending, so the levels never cross; the raw
+        decoder output otherwise (with ``return_local`` also the per-node
+        local prediction ``[N,1]``).  Same embed, QKVS GEMM, pool and decoder ops
         as ``SAGEDeterministic.forward``; each conv is the QKVS GEMM plus
         the forward-only attention kernel with the cached P tables, the
         folded BN of the layer and the ReLU in its epilogue.  CPU batches
@@ -164,7 +181,11 @@ class Predictor:
         g = torch.cat([mean_x, entry_vec], dim=1)
         hid = ops.linear(g, m.global_linear1.weight, m.global_linear1.bias)
         pred = ops.linear(tF.relu(hid), m.global_linear2.weight,
-                          m.global_linear2.bias).flatten().float()
+                          m.global_linear2.bias).float()
+        if self.num_quantiles == 1:
+            pred = pred.flatten()
+        elif rearrange:
+            pred = ops.quantile_rearrange(pred)
         if return_local:
             local = ops.linear(x, m.local_linear.weight, m.local_linear.bias)
             return pred, local
@@ -186,32 +207,40 @@ class Predictor:
                 and len(batches) == len(self._batches)
                 and all(a is c for a, c in zip(batches, self._batches)))
 
-    def predict(self, batches):
+    def predict(self, batches, rearrange: bool = True):
         """Predictions for every batch, concatenated in order into one fp32
-        CPU tensor.  One host sync, at the end."""
+        CPU tensor (``[n]``, or ``[n, Q]`` for Q > 1 levels).  One host
+        sync, at the end."""
         if self.captured_over(batches):
-            outs = [self.replay(i) for i in range(len(self._batches))]
+            outs = [self.replay(i, rearrange=rearrange)
+                    for i in range(len(self._batches))]
         else:
             outs = []
             for b in batches:
                 if b.x.device != self.device:
                     b = b.to(self.device)
-                outs.append(self.predict_batch(b))
+                outs.append(self.predict_batch(b, rearrange=rearrange))
         if not outs:
-            return torch.empty(0, dtype=torch.float32)
+            return torch.empty((0,) if self.num_quantiles == 1
+                               else (0, self.num_quantiles),
+                               dtype=torch.float32)
         return torch.cat(outs).cpu()
 
     def capture(self, resident_batches):
         """Capture the forward of every resident batch into its own hipGraph
         (one shared memory pool), after an eager warm-up pass that primes
-        the allocator.  Each batch gets a static output buffer; ``replay(i)``
-        returns it.  The captured forward runs on a single stream with no
+        the allocator.  Each batch gets a static output buffer
+        (``[num_graphs]``, or ``[num_graphs, Q]`` for Q > 1 levels);
+        ``replay(i)`` returns it.  For Q > 1 the graph ends with the
+        rearrangement kernel and keeps the raw decoder output in a second
+        static buffer for ``replay(i, rearrange=False)``.  The captured forward runs on a single stream with no
         parallel branches.  On CPU the predictor keeps stepping eagerly.
         Returns ``mode``: ``"graph"`` or ``"eager"``.  A capture failure is
         raised to the caller — there is no silent eager fallback."""
         batches = list(resident_batches)
         self._graphs = None
         self._out = None
+        self._raw = None
         self._batches = batches  # held: keeps the ids below unique
         self._index = {id(b): i for i, b in enumerate(batches)}
         if not self._fused:
@@ -220,18 +249,23 @@ class Predictor:
         for b in batches:
             if not use_hip(b.x):
                 raise ValueError("capture() needs device-resident batches")
-        outs = [torch.empty(b.num_graphs, dtype=torch.float32,
-                            device=self.device) for b in batches]
+        nq = self.num_quantiles
+        outs = [torch.empty((b.num_graphs,) if nq == 1 else (b.num_graphs, nq),
+                            dtype=torch.float32, device=self.device)
+                for b in batches]
+        raws = [torch.empty_like(o) for o in outs] if nq > 1 else outs
         for b in batches:  # allocation warm-up (eager)
             self.predict_batch(b)
         torch.cuda.synchronize()
         graphs = []
         pool = None
         try:
-            for b, out in zip(batches, outs):
+            for b, out, raw in zip(batches, outs, raws):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool):
-                    out.copy_(self.predict_batch(b))
+                    raw.copy_(self.predict_batch(b, rearrange=False))
+                    if nq > 1:  # the sort is the graph's last op
+                        out.copy_(ops.quantile_rearrange(raw))
                 if pool is None:
                     pool = g.pool()
                 graphs.append(g)
@@ -243,20 +277,23 @@ class Predictor:
         torch.cuda.synchronize()
         self._graphs = graphs
         self._out = outs
+        self._raw = raws
         self.mode = "graph"
         return self.mode
 
-    def replay(self, i: int):
+    def replay(self, i: int, rearrange: bool = True):
         """Prediction for resident batch ``i`` of the last ``capture()``:
         replays its graph and returns the batch's static output buffer (the
-        next ``replay(i)`` overwrites it); eager mode computes it afresh."""
+        next ``replay(i)`` overwrites it); eager mode computes it afresh.
+        ``rearrange=False`` returns the raw decoder output instead of the
+        sorted rows (the same thing for a one-level model)."""
         if self._batches is None:
             raise RuntimeError("replay() before capture()")
         if self._graphs is None:
-            return self.predict_batch(self._batches[i])
+            return self.predict_batch(self._batches[i], rearrange=rearrange)
         self._check_precision()
         self._graphs[i].replay()
-        return self._out[i]
+        return self._out[i] if rearrange else self._raw[i]
 
 
 __all__ = ["fold_bn", "Predictor"]

@@ -287,7 +287,12 @@ class TransformerConv(nn.Module):
 class SAGEDeterministic(nn.Module):
     """API- and checkpoint-compatible with reference model.py:10-114.
     ``heads`` (keyword-only, default 1 = the reference) is the attention
-    head count of every conv; it must divide ``hidden_channels``."""
+    head count of every conv; it must divide ``hidden_channels``.
+    ``num_quantiles`` (keyword-only, default 1 = the reference) is the width
+    of the global decoder's output: ``forward`` returns ``global_predict
+    [B, num_quantiles]``, one column per quantile level.  ``taus`` holds the
+    levels the model is trained for (set by the CLI and the checkpoint
+    loader; None = unknown)."""
 
     def __init__(
         self,
@@ -301,9 +306,15 @@ class SAGEDeterministic(nn.Module):
         dropout,
         *,
         heads=1,
+        num_quantiles=1,
     ):
         super().__init__()
+        if not isinstance(num_quantiles, int) or not 1 <= num_quantiles <= 8:
+            raise ValueError(
+                f"num_quantiles={num_quantiles!r} must be an integer in 1..8")
         self.heads = heads
+        self.num_quantiles = num_quantiles
+        self.taus = None
         self.convs = nn.ModuleList()
         self.convs.append(
             TransformerConv(
@@ -335,7 +346,7 @@ class SAGEDeterministic(nn.Module):
         )
         self.local_linear = nn.Linear(hidden_channels, 1)
         self.global_linear1 = nn.Linear(hidden_channels * 2, hidden_channels)
-        self.global_linear2 = nn.Linear(hidden_channels, 1)
+        self.global_linear2 = nn.Linear(hidden_channels, num_quantiles)
         self.cat_embedding = nn.ModuleList()
         for num_categories in cat_dims:
             self.cat_embedding.append(nn.Embedding(num_categories, hidden_channels))

@@ -1404,16 +1404,116 @@ class _QuantileLossFn(torch.autograd.Function):
         return None, dy_hat, None
 
 
+def _is_level(tau) -> bool:
+    """True for one scalar level (a number or a 0-d tensor), False for a
+    sequence of levels."""
+    if torch.is_tensor(tau):
+        return tau.dim() == 0
+    return not hasattr(tau, "__len__") and not hasattr(tau, "__iter__")
+
+
+def quantile_loss_parts(y, y_hat, taus):
+    """``(loss, per_level_sums)`` for ``y [B]``, ``y_hat [B, Q]`` and Q
+    levels: the pinball loss summed over levels and averaged over rows, and
+    the undivided pinball sum of every level ``[Q]`` (no gradient)."""
+    levels = ref.check_taus(taus)
+    ref._check_multi(y, y_hat, levels)
+    if use_hip(y_hat):
+        # STOPGAP until single-pass multi-level kernels exist: one launch of
+        # the scalar HIP loss per level, each on its own contiguous column.
+        # Every level sees the gradient scale g/B it would have alone, and
+        # one level is the scalar op bit for bit.
+        cols = [y_hat[:, q].contiguous() for q in range(len(levels))]
+        losses = [_QuantileLossFn.apply(y, c, t) for c, t in zip(cols, levels)]
+        if len(losses) == 1:
+            loss = losses[0]
+        else:
+            # the levels are added in fp64 and rounded to fp32 once, so the
+            # sum costs one rounding, not Q - 1
+            loss = torch.stack(losses).double().sum().float()
+        if y.shape[0] == 0:
+            return loss, y_hat.new_zeros(len(levels))
+        # the undivided per-level sums come from the scalar metric kernel
+        # (loss_q * B would round twice more at a B that is no power of two)
+        with torch.no_grad():
+            sums = torch.stack([ext().eval_metrics(y, c.detach(), t)[2]
+                                for c, t in zip(cols, levels)])
+        return loss, sums
+    loss, sums = ref.quantile_loss_multi(y, y_hat, levels)
+    return loss, sums.detach()
+
+
 def quantile_loss(y, y_hat, tau):
+    """Pinball loss.  A scalar ``tau`` takes ``[B]`` predictions; a sequence
+    of Q levels takes ``[B, Q]`` predictions and sums the levels."""
+    if not _is_level(tau):
+        return quantile_loss_parts(y, y_hat, tau)[0]
+    if y_hat.dim() != y.dim():
+        raise ValueError(
+            f"a scalar tau takes predictions shaped like y {tuple(y.shape)}, "
+            f"got {tuple(y_hat.shape)}; pass the levels as a sequence for "
+            "[B, Q] predictions")
     if use_hip(y_hat):
         return _QuantileLossFn.apply(y, y_hat, tau)
     return ref.quantile_loss(y, y_hat, tau)
 
 
 def eval_metrics(y, y_hat, tau):
+    """Scalar ``tau``: the (mae, mape, pinball) sums.  A sequence of Q
+    levels with ``[B, Q]`` predictions: the ``[3 + 2Q]`` vector ``[mae,
+    mape, crossing rows, pinball[Q], covered rows[Q]]`` with MAE/MAPE of the
+    point level.  The counts are fp32 sums of ones: exact below 2^24 rows
+    per call."""
+    if not _is_level(tau):
+        levels = ref.check_taus(tau)
+        ref._check_multi(y, y_hat, levels)
+        point = ref.point_level(levels)
+        if use_hip(y_hat):
+            # STOPGAP until a single-pass kernel exists: the scalar HIP
+            # metric reduction once per level; the two counts are
+            # comparisons summed by torch (evaluation only)
+            cols = [ext().eval_metrics(y, y_hat[:, q].contiguous(), t)
+                    for q, t in enumerate(levels)]
+            cross = (y_hat[:, 1:] < y_hat[:, :-1]).any(dim=1).sum()
+            cover = (y.unsqueeze(1) <= y_hat).sum(dim=0)
+            return torch.cat([
+                torch.stack([cols[point][0], cols[point][1],
+                             cross.to(y_hat.dtype)]),
+                torch.stack([c[2] for c in cols]),
+                cover.to(y_hat.dtype)])
+        return ref.eval_metrics_multi(y, y_hat, levels, point)
+    if y_hat.dim() != y.dim():
+        raise ValueError(
+            f"a scalar tau takes predictions shaped like y {tuple(y.shape)}, "
+            f"got {tuple(y_hat.shape)}")
     if use_hip(y_hat):
         return ext().eval_metrics(y, y_hat, tau)
     return ref.eval_metrics(y, y_hat, tau)
+
+
+def quantile_rearrange(y_hat):
+    """Rows of ``[B, Q]`` predictions sorted ascending (Q = 1: the input
+    itself, nothing launched)."""
+    if y_hat.dim() != 2:
+        raise ValueError(f"expected y_hat [B, Q], got {tuple(y_hat.shape)}")
+    if y_hat.shape[1] > ref.MAX_QUANTILES:
+        raise ValueError(f"at most {ref.MAX_QUANTILES} levels are supported, "
+                         f"got {y_hat.shape[1]}")
+    if y_hat.shape[1] == 1:
+        return y_hat
+    if use_hip(y_hat):
+        # STOPGAP until a HIP kernel exists: torch elementwise min/max over
+        # the columns in odd-even transposition order (Q stages).  They
+        # move values and compute none, and need no sort temporaries, so
+        # the Predictor can capture them in its hipGraph
+        cols = list(y_hat.unbind(dim=1))
+        for stage in range(len(cols)):
+            for j in range(stage & 1, len(cols) - 1, 2):
+                lo = torch.minimum(cols[j], cols[j + 1])
+                cols[j + 1] = torch.maximum(cols[j], cols[j + 1])
+                cols[j] = lo
+        return torch.stack(cols, dim=1)
+    return ref.quantile_rearrange(y_hat)
 
 
 # ---------------------------------------------------------------------------
@@ -1538,6 +1638,8 @@ __all__ = [
     "embed_concat_edge",
     "batchnorm_relu",
     "quantile_loss",
+    "quantile_loss_parts",
+    "quantile_rearrange",
     "eval_metrics",
     "linear",
 ]

@@ -199,3 +199,96 @@ def eval_metrics(y: torch.Tensor, y_hat: torch.Tensor, tau: float):
     e = y - y_hat
     q_sum = torch.maximum(tau * e, (tau - 1) * e).sum()
     return mae_sum, mape_sum, q_sum
+
+
+# ---------------------------------------------------------------------------
+# multi-level quantile heads: y [B], y_hat [B, Q], taus 1..8 increasing levels
+# ---------------------------------------------------------------------------
+
+MAX_QUANTILES = 8
+
+
+def check_taus(taus) -> tuple:
+    """``taus`` as a tuple of floats: 1..8 strictly increasing levels in
+    (0, 1); anything else is a ValueError."""
+    try:
+        levels = tuple(float(t) for t in taus)
+    except TypeError:
+        raise ValueError(f"taus must be a sequence of levels, got {taus!r}") from None
+    if not 1 <= len(levels) <= MAX_QUANTILES:
+        raise ValueError(
+            f"taus must hold 1..{MAX_QUANTILES} levels, got {len(levels)}: {levels}")
+    for q, t in enumerate(levels):
+        if not 0.0 < t < 1.0:  # also refuses NaN
+            raise ValueError(f"taus[{q}]={t} is outside (0, 1)")
+        if q and not t > levels[q - 1]:
+            raise ValueError(f"taus must be strictly increasing, got {levels}")
+    return levels
+
+
+def point_level(taus) -> int:
+    """Index of the level closest to 0.5 (the lower index on a tie): the
+    column MAE and MAPE are reported for."""
+    levels = check_taus(taus)
+    return min(range(len(levels)), key=lambda q: (abs(levels[q] - 0.5), q))
+
+
+def _check_multi(y: torch.Tensor, y_hat: torch.Tensor, levels: tuple):
+    if y.dim() != 1 or y_hat.dim() != 2:
+        raise ValueError(
+            f"expected y [B] and y_hat [B, Q], got {tuple(y.shape)} and "
+            f"{tuple(y_hat.shape)}")
+    if y_hat.shape[0] != y.shape[0] or y_hat.shape[1] != len(levels):
+        raise ValueError(
+            f"y_hat {tuple(y_hat.shape)} does not match y {tuple(y.shape)} "
+            f"and {len(levels)} levels")
+
+
+def _pinball_terms(y, y_hat, levels):
+    tau = torch.tensor(levels, dtype=y_hat.dtype, device=y_hat.device)
+    e = y.unsqueeze(1) - y_hat
+    return torch.maximum(tau * e, (tau - 1) * e)
+
+
+def quantile_loss_multi(y: torch.Tensor, y_hat: torch.Tensor, taus):
+    """(loss, per_level_sums): the pinball loss summed over the Q levels and
+    averaged over the B rows, and the undivided pinball sum of every level
+    ``[Q]``.  Q = 1 is ``quantile_loss``; B = 0 gives NaN and zeros."""
+    levels = check_taus(taus)
+    _check_multi(y, y_hat, levels)
+    terms = _pinball_terms(y, y_hat, levels)
+    sums = terms.sum(dim=0)
+    if y.shape[0] == 0:
+        return sums.sum() + float("nan"), sums
+    return sums.sum() / y.shape[0], sums
+
+
+def eval_metrics_multi(y: torch.Tensor, y_hat: torch.Tensor, taus,
+                       point: int | None = None) -> torch.Tensor:
+    """``[3 + 2Q]`` sums: ``[mae, mape, crossing rows, pinball[Q],
+    covered rows[Q]]``.  MAE and MAPE are of column ``point`` (default
+    ``point_level(taus)``), MAPE divides by y as it is (quirk 13); level q
+    covers row i when ``y_i <= y_hat_iq``; a row crosses when any of its
+    predictions is below the one before it."""
+    levels = check_taus(taus)
+    _check_multi(y, y_hat, levels)
+    if point is None:
+        point = point_level(levels)
+    abs_err = (y_hat[:, point] - y).abs()
+    cross = (y_hat[:, 1:] < y_hat[:, :-1]).any(dim=1)
+    cover = y.unsqueeze(1) <= y_hat
+    dt = y_hat.dtype
+    return torch.cat([
+        torch.stack([abs_err.sum(), (abs_err / y).sum(), cross.to(dt).sum()]),
+        _pinball_terms(y, y_hat, levels).sum(dim=0),
+        cover.to(dt).sum(dim=0),
+    ])
+
+
+def quantile_rearrange(y_hat: torch.Tensor) -> torch.Tensor:
+    """Every row sorted ascending: the monotone rearrangement of crossing
+    quantile predictions.  With increasing levels it never increases a
+    row's summed pinball loss."""
+    if y_hat.dim() != 2:
+        raise ValueError(f"expected y_hat [B, Q], got {tuple(y_hat.shape)}")
+    return torch.sort(y_hat, dim=1).values

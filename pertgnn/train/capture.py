@@ -16,8 +16,8 @@ equivalent in expectation but not step-identical — leave the flag off for
 exact-reference semantics.
 
 Per-epoch metrics accumulate on device INSIDE the captured graph ([loss*B,
-sum |err|/y] into a persistent accumulator), so an epoch costs one host
-sync.  World-size > 1 uses the compute-only capture with an eager gradient
+sum |err|/y] into a persistent accumulator, with a sequence of quantile
+levels also every level's pinball sum), so an epoch costs one host sync.  World-size > 1 uses the compute-only capture with an eager gradient
 all-reduce + optimizer tail (the same safe 'split' schedule bench.py
 defaults to over RCCL); world-size 1 captures the optimizer step too.  On
 CPU (tests) the stepper degrades to eager stepping over the same fixed
@@ -28,6 +28,7 @@ from __future__ import annotations
 import torch
 
 from ..ops import functional as F
+from ..ops import reference as ref
 
 
 class GraphStepper:
@@ -42,7 +43,13 @@ class GraphStepper:
         self.loss_scale = loss_scale
         self.batches = batches
         self.on_gpu = device is not None and device.type == "cuda"
-        self.acc = torch.zeros(2, dtype=torch.float32,
+        # a sequence of Q levels trains on the pinball loss summed over them;
+        # the accumulator then also carries the per-level pinball sums
+        self.levels = None if F._is_level(tau) else ref.check_taus(tau)
+        self.point = ref.point_level(self.levels) if self.levels else 0
+        self.last_q_loss = None  # per-level averages of the last epoch
+        self.acc = torch.zeros(2 + (len(self.levels) if self.levels else 0),
+                               dtype=torch.float32,
                                device=device if self.on_gpu else "cpu")
         self.generator = torch.Generator().manual_seed(seed)
         self.n_graphs = sum(b.num_graphs for b in batches)
@@ -56,8 +63,12 @@ class GraphStepper:
         gp, _ = self.model(b.x, b.cat_X, b.edge_index, b.edge_attr,
                            b.pattern_num_nodes, b.rt_probs, b.entry_id,
                            b.batch, csr=b.csr, num_graphs=b.num_graphs)
-        pred = gp.flatten()
-        loss = F.quantile_loss(b.y, pred, self.tau)
+        if self.levels is None:
+            pred = gp.flatten()
+            loss = F.quantile_loss(b.y, pred, self.tau)
+        else:
+            loss, q_sums = F.quantile_loss_parts(b.y, gp, self.levels)
+            pred = gp[:, self.point]
         if hasattr(self.optimizer, "scale_loss"):
             self.optimizer.scale_loss(loss).backward()
         elif self.loss_scale != 1.0:
@@ -67,6 +78,8 @@ class GraphStepper:
         with torch.no_grad():
             self.acc[0] += loss.detach() * b.num_graphs
             self.acc[1] += ((pred.detach() - b.y).abs() / b.y).sum()
+            if self.levels is not None:
+                self.acc[2:] += q_sums
         return loss
 
     def _full_step(self, i):
@@ -181,7 +194,10 @@ class GraphStepper:
                 self.optimizer.step()
         if self.on_gpu:
             torch.cuda.synchronize()
-        total_loss, mape_sum = self.acc.tolist()
+        total_loss, mape_sum, *level_sums = self.acc.tolist()
+        if self.levels is not None:
+            # rank-local, like the sums returned
+            self.last_q_loss = [v / max(self.n_graphs, 1) for v in level_sums]
         return total_loss, mape_sum, self.n_graphs
 
     def run_epoch(self):
