@@ -2,6 +2,10 @@
 and hipBLASLt (torch bf16 matmul) at the trace-scale model shapes.
 
     python benchmarks/glds_bench.py [--iters 50]
+
+``--fwd-variants`` times only the k = 256 forward on its kernels: the
+streaming glds NT kernel and the A-resident one in both geometries
+(``--m`` rows, default 45 056 and 180 762; n = 1024), interleaved ``--rounds``.
 """
 import argparse
 import sys
@@ -24,13 +28,56 @@ def bench(fn, iters, *args):
     return (time.perf_counter() - t0) / iters
 
 
+def fwd_variants(C, dev, iters, rounds, ms):
+    """The k = 256 forward on the streaming and the A-resident kernel (both
+    geometries), interleaved rounds in one process; y checked bit for bit."""
+    import os
+
+    arms = [("stream", 1, None), ("resident G1", 2, "1"),
+            ("resident G2", 2, "2")]
+    n, k = 1024, 256
+    print(f"{'fwd variant':<14} {'M':>7}  " +
+          "  ".join(f"r{r + 1:>2}(us)" for r in range(rounds)) + "    min")
+    for m in ms:
+        x = (torch.randn(m, k, device=dev) * 0.5).to(torch.bfloat16)
+        w = torch.randn(n, k, device=dev) * 0.1
+        b = torch.randn(n, device=dev)
+        times = {name: [] for name, _, _ in arms}
+        ys = {}
+        for _ in range(rounds):
+            for name, v, geom in arms:
+                if geom is None:
+                    os.environ.pop("PERTGNN_FWD_RES_GEOM", None)
+                else:
+                    os.environ["PERTGNN_FWD_RES_GEOM"] = geom
+                ys[name] = C.linear_fwd_a16o16(x, w, b, False, v)
+                # the weight-convert launch (about 2 us) is part of every arm
+                times[name].append(bench(C.linear_fwd_a16o16, iters, x, w, b,
+                                         False, v))
+        os.environ.pop("PERTGNN_FWD_RES_GEOM", None)
+        for name, _, _ in arms:
+            same = torch.equal(ys[name].view(torch.int16),
+                               ys["stream"].view(torch.int16))
+            t = times[name]
+            print(f"{name:<14} {m:>7}  " +
+                  "  ".join(f"{v * 1e6:7.1f}" for v in t) +
+                  f"  {min(t) * 1e6:7.1f}  bits={'same' if same else 'DIFFER'}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--fwd-variants", action="store_true",
+                    help="only the forward kernel variants at k = 256")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--m", type=int, nargs="*", default=[45056, 180762])
     args = ap.parse_args()
     import pertgnn._C as C
 
     dev = torch.device("cuda:0")
+    if args.fwd_variants:
+        fwd_variants(C, dev, args.iters, args.rounds, args.m)
+        return
     # (name, M, N(out), K): qkvs fwd + dgrad at the realistic bench scale
     shapes = [
         ("qkvs fwd", 180736, 1024, 256),

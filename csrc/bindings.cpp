@@ -274,6 +274,10 @@ void launch_gemm_a16_glds_tn(const void*, const void*, float*, float*, int,
 // supports: `tile` if forced (-1 where the shape does not allow it), else
 // the process-wide override or the dispatch's choice
 int glds_tn_tile_for(int m, int n, int k2, int tile);
+void launch_gemm_a16_resident_nt(const void*, const void*, const float*, void*,
+                                 int, int, int, hipStream_t);
+int fwd_variant_for(int m, int n, int k);
+void set_fwd_variant_hook(int v);
 void set_glds_tn_tile(int tile);
 void launch_transpose_convert_w16(const float*, void*, int, int, hipStream_t);
 void launch_gemm_skinny_nn(const void*, const float*, float*, int, int, int,
@@ -1713,12 +1717,37 @@ static std::vector<torch::Tensor> linear_fwd_a16o16_impl(torch::Tensor x,
                                                          torch::Tensor w,
                                                          torch::Tensor b,
                                                          bool fp16c,
-                                                         bool want_wt) {
+                                                         bool want_wt,
+                                                         int64_t variant = 0,
+                                                         OptTensor out =
+                                                             std::nullopt) {
+  namespace gd = gemm_dispatch;
   CHECK_IN(x); CHECK_IN(w);
   const int m = x.size(0);
   const int k = x.size(1);
   const int n = w.size(0);
-  auto y = torch::empty({m, n}, x.options());  // bf16
+  // variant != 0 forces the streaming (1) or the A-resident (2) glds kernel
+  // for any shape that kernel can run; out, if given, receives y in its
+  // first m rows (a test hook: the rows behind them must stay untouched)
+  TORCH_CHECK(variant == gd::FWD_AUTO ||
+                  (!fp16c && variant == gd::FWD_STREAM &&
+                   gd::fwd_stream_can(m, n, k)) ||
+                  (!fp16c && variant == gd::FWD_RESIDENT &&
+                   gd::fwd_resident_can(m, n, k)),
+              "linear_fwd_a16o16: variant ", variant, " cannot run [", m, ", ",
+              k, "] x [", n, ", ", k, "]^T (1 needs bf16 compute, n % 128 == "
+              "0 and k % 32 == 0; 2 needs bf16 compute, n % 128 == 0 and k == "
+              "256)");
+  torch::Tensor y;
+  if (out.has_value() && out->defined()) {
+    CHECK_IN((*out));
+    TORCH_CHECK(out->scalar_type() == torch::kBFloat16 && out->dim() == 2 &&
+                    out->size(0) >= m && out->size(1) == n,
+                "out must be bf16 [>= m, n]");
+    y = out->narrow(0, 0, m);
+  } else {
+    y = torch::empty({m, n}, x.options());  // bf16
+  }
   auto wt16 = torch::empty({0}, x.options());
   if (m == 0) return {y, wt16};  // no rows: nothing to launch
   const float* bias = nullptr;
@@ -1731,7 +1760,9 @@ static std::vector<torch::Tensor> linear_fwd_a16o16_impl(torch::Tensor x,
   // glds fast path (direct-to-LDS staging): needs 16-B-aligned rows, full
   // BK tiles in k, and n a multiple of the 128-wide tile.  The bf16 weight
   // copy costs one trivial convert kernel per call (n*k elements).
-  if (gemm_dispatch::fwd_glds_ok(m, n, k)) {
+  const int fv = variant != gd::FWD_AUTO ? (int)variant
+                                         : fwd_variant_for(m, n, k);
+  if (fv != 0) {
     auto w16 = torch::empty({n, k}, x.options());  // bf16
     if (want_wt && dgrad_glds_ok(m, n, k)) {
       wt16 = torch::empty({k, n}, x.options());  // bf16, transposed
@@ -1741,8 +1772,13 @@ static std::vector<torch::Tensor> linear_fwd_a16o16_impl(torch::Tensor x,
       launch_convert_w16(w.data_ptr<float>(), w16.data_ptr(), (long)n * k,
                          cur_stream());
     }
-    launch_gemm_a16_glds_nt(x.data_ptr(), w16.data_ptr(), bias, y.data_ptr(),
-                            /*c16=*/1, m, n, k, false, cur_stream());
+    if (fv == gd::FWD_RESIDENT)
+      launch_gemm_a16_resident_nt(x.data_ptr(), w16.data_ptr(), bias,
+                                  y.data_ptr(), m, n, k, cur_stream());
+    else
+      launch_gemm_a16_glds_nt(x.data_ptr(), w16.data_ptr(), bias,
+                              y.data_ptr(), /*c16=*/1, m, n, k, false,
+                              cur_stream());
     return {y, wt16};
   }
   launch_gemm_bf16_nt_a16o16(x.data_ptr(), w.data_ptr<float>(), bias,
@@ -1766,8 +1802,10 @@ std::vector<torch::Tensor> convert_w16_both(torch::Tensor w) {
 }
 
 torch::Tensor linear_fwd_a16o16(torch::Tensor x, torch::Tensor w,
-                                torch::Tensor b, bool fp16c = false) {
-  return linear_fwd_a16o16_impl(x, w, b, fp16c, false)[0];
+                                torch::Tensor b, bool fp16c = false,
+                                int64_t variant = 0,
+                                OptTensor out = std::nullopt) {
+  return linear_fwd_a16o16_impl(x, w, b, fp16c, false, variant, out)[0];
 }
 
 std::vector<torch::Tensor> linear_fwd_a16o16_wt(torch::Tensor x,
@@ -1954,6 +1992,30 @@ void set_wgrad_tile(int64_t tile) {
   TORCH_CHECK(tile >= 0 && tile <= gemm_dispatch::TN_256x256,
               "set_wgrad_tile: tile must be 0 (auto), 1, 2 or 3");
   set_glds_tn_tile((int)tile);
+}
+
+// Kernel of the glds forward (linear_fwd_a16o16, bf16 compute) at a shape, as
+// it runs in this process: "stream" (every block stages its own A K-tiles),
+// "resident" (a block keeps its A row tile in LDS and sweeps the column
+// tiles), or "none" where the shape is not on the glds forward.  Both give
+// the same bits and share linear_path's label; unlike linear_path this
+// follows set_fwd_variant and PERTGNN_NO_FWD_RESIDENT.
+std::string fwd_variant(int64_t m, int64_t n, int64_t k) {
+  TORCH_CHECK(m >= 0 && n > 0 && k > 0 && m <= INT_MAX && n <= INT_MAX &&
+                  k <= INT_MAX, "fwd_variant: bad shape");
+  const int v = m == 0 ? 0 : fwd_variant_for((int)m, (int)n, (int)k);
+  return v == gemm_dispatch::FWD_RESIDENT ? "resident"
+         : v == gemm_dispatch::FWD_STREAM ? "stream" : "none";
+}
+
+// Test hook: the kernel every later glds forward of this process takes where
+// the A-resident kernel can run the shape, rows below the glds gate included
+// (0: back to the dispatch's choice).
+void set_fwd_variant(int64_t variant) {
+  TORCH_CHECK(variant >= 0 && variant <= gemm_dispatch::FWD_RESIDENT,
+              "set_fwd_variant: variant must be 0 (auto), 1 (stream) or 2 "
+              "(resident)");
+  set_fwd_variant_hook((int)variant);
 }
 
 // Every label linear_path can return, as "io|prec|op|label"; the wgrad labels
@@ -2308,7 +2370,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("seg_pool_fwd16", &seg_pool_fwd16);
   mod.def("seg_pool_bwd16", &seg_pool_bwd16);
   mod.def("linear_fwd_a16o16", &linear_fwd_a16o16, py::arg("x"), py::arg("w"),
-          py::arg("b"), py::arg("fp16c") = false);
+          py::arg("b"), py::arg("fp16c") = false, py::arg("variant") = 0,
+          py::arg("out") = py::none());
+  mod.def("fwd_variant", &fwd_variant, py::arg("m"), py::arg("n"),
+          py::arg("k"));
+  mod.def("set_fwd_variant", &set_fwd_variant, py::arg("variant"));
   mod.def("convert_w16_both", &convert_w16_both, py::arg("w"));
   mod.def("linear_fwd_a16o16_wt", &linear_fwd_a16o16_wt, py::arg("x"),
           py::arg("w"), py::arg("b"), py::arg("fp16c") = false);

@@ -1104,6 +1104,191 @@ __global__ void gemm_a16_glds_nt_kernel(const __bf16* __restrict__ a,
   }
 }
 
+// ---------------------------------------------------------------------------
+// A-resident glds NT kernel (forward with a short K and a wide output): one
+// block owns a BM-row tile of A for the whole call and sweeps all n / 128
+// column tiles.  The kernel above stages every A row tile once per column
+// tile and pays a barrier per 32 of K; here the BM x KT tile is staged once,
+// as KT/32 slabs in that kernel's lane-linear [BM][32] image (same glds_swz
+// on both sides, rows past m clamped to m - 1), and is never restaged, so A
+// has no WAR hazard.  The weight image (L2-resident) streams through a ring
+// of two [128 cols][BKB k] stages, each BKB/32 slabs of the [128][32] image:
+//   issue stage t+1 -> MFMA stage t -> s_waitcnt vmcnt(0) -> barrier
+// which is the streaming kernel's sync structure at BKB/32 times the MFMAs
+// per barrier.  RAW: a stage is read only after the vmcnt(0) + barrier that
+// follow its issue.  WAR: stage t+1 overwrites the buffer read in iteration
+// t-1, whose ds_reads all fed MFMAs issued before that iteration's barrier.
+// Per output element the MFMA chain is the streaming kernel's (16x16x32, k
+// ascending in steps of 32, one accumulator), as are the bias add and the
+// single rounding, so C is bit-equal to it on any input.
+// Waves are (BM/32) x 2 with a 32 x 64 wave tile: the epilogue transposes a
+// 16-row band through a per-wave scratch of its own (the A tile stays live)
+// and every 16-B-per-lane store instruction covers 8 whole 128-B lines.
+// The epilogue of a column tile runs after the barrier that ends its last
+// stage, so its stores drain behind the next tile's MFMAs and the ordinary
+// bias loads never meet a glds in flight.
+// Requires k == KT, n % 128 == 0, 16-B-aligned rows; any m >= 1.
+// Reads stay in bounds: A rows are clamped, the last A slab ends at byte
+// KT * 2 of its row, B rows end at n0 + 128 <= n and B slabs at k.
+// ---------------------------------------------------------------------------
+template <int BM, int KT, int BKB, bool NTC>
+__launch_bounds__(BM * 4)
+__global__ void gemm_a16_resident_nt_kernel(const __bf16* __restrict__ a,
+                                            const __bf16* __restrict__ b,
+                                            const float* __restrict__ bias,
+                                            __bf16* __restrict__ c, int m,
+                                            int n) {
+  constexpr int BN = 128;
+  constexpr int THREADS = BM * 4;
+  constexpr int NWAVE = THREADS / PERTGNN_WAVE;      // BM / 16
+  constexpr int FM = 2, FN = 4;                      // 32 x 64 wave tile
+  constexpr int SLAB_A = BM * 64;                    // [BM][32] bf16
+  constexpr int SLAB_B = BN * 64;                    // [128][32] bf16
+  constexpr int NSLAB = BKB / 32;                    // slabs per B stage
+  constexpr int KS = KT / BKB;                       // B stages per tile
+  constexpr int A_BYTES = (KT / 32) * SLAB_A;
+  constexpr int B_BYTES = NSLAB * SLAB_B;
+  constexpr int GRPS_B = B_BYTES / 1024;             // 1 KiB per wave-glds
+  constexpr int BNW = 64;                            // wave's output columns
+  constexpr int SW = BNW + 8;                        // padded scratch stride
+  static_assert(SLAB_A / 1024 == NWAVE, "one glds per wave per A slab");
+  static_assert(KS % 2 == 0 && GRPS_B % NWAVE == 0, "ring of two stages");
+  // one arena: [A tile][B0 B1][per-wave C scratch]
+  __shared__ char smem[A_BYTES + 2 * B_BYTES + NWAVE * 16 * SW * 2];
+  char* const lds_a = smem;
+  const auto lds_bb = [&](int i) { return smem + A_BYTES + i * B_BYTES; };
+  const int m0 = blockIdx.x * BM;
+  const int wave = threadIdx.x / PERTGNN_WAVE;
+  const int lane = threadIdx.x % PERTGNN_WAVE;
+  const int wm = (wave / 2) * 32;
+  const int wn = (wave % 2) * BNW;
+
+  // per-lane glds source mapping of the [rows][32] image (see above): one
+  // 1-KiB group covers 16 rows of 64 B
+  const unsigned l_off = glds_swz((unsigned)lane * 16);
+  const int src_row = (int)(l_off / 64);
+  const int src_kb = (int)(l_off % 64);
+  const long ldb = (long)KT * 2;                     // row bytes, A and B
+
+  const auto glds16 = [](const char* src, char* dst) {
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) void*)src,
+        (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+  };
+  // B stage t = (column tile, ks): group g is rows (g % 8) * 16 .. of slab
+  // g / 8
+  const auto stage_b = [&](int n0, int ks, char* lds) {
+#pragma unroll
+    for (int i = 0; i < GRPS_B / NWAVE; ++i) {
+      const int grp = wave + i * NWAVE;
+      const int row = n0 + (grp % 8) * 16 + src_row;
+      const int kb = (ks * BKB + (grp / 8) * 32) * 2 + src_kb;
+      glds16((const char*)b + (long)row * ldb + kb, lds + grp * 1024);
+    }
+  };
+
+  {
+    const int row = min(m0 + wave * 16 + src_row, m - 1);
+    const char* src = (const char*)a + (long)row * ldb + src_kb;
+#pragma unroll
+    for (int s = 0; s < KT / 32; ++s)
+      glds16(src + s * 64, lds_a + s * SLAB_A + wave * 1024);
+  }
+  stage_b(0, 0, lds_bb(0));
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+
+  const int fi = lane & 15;
+  const int kb = (lane >> 4) * 16;                   // fragment k byte
+  const int fcol = lane & 15;
+  const int frow = (lane >> 4) * 4;
+  __bf16* scratch = reinterpret_cast<__bf16*>(smem + A_BYTES + 2 * B_BYTES +
+                                              wave * 16 * SW * 2);
+  const int tiles_n = n / BN;
+  for (int ct = 0; ct < tiles_n; ++ct) {
+    const int n0 = ct * BN;
+    f32x4 acc[FM][FN];
+#pragma unroll
+    for (int i = 0; i < FM; ++i)
+#pragma unroll
+      for (int j = 0; j < FN; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      // next stage into the other buffer (KS is even: buffer = ks & 1)
+      if (ks + 1 < KS)
+        stage_b(n0, ks + 1, lds_bb((ks + 1) & 1));
+      else if (ct + 1 < tiles_n)
+        stage_b(n0 + BN, 0, lds_bb(0));
+      const char* lb = lds_bb(ks & 1);
+#pragma unroll
+      for (int s = 0; s < NSLAB; ++s) {
+        const char* la = lds_a + (ks * NSLAB + s) * SLAB_A;
+        bf16x8 av[FM], bv[FN];
+#pragma unroll
+        for (int mi = 0; mi < FM; ++mi) {
+          const int row = wm + mi * 16 + fi;
+          av[mi] = *reinterpret_cast<const bf16x8*>(
+              la + glds_swz((unsigned)(row * 64 + kb)));
+        }
+#pragma unroll
+        for (int ni = 0; ni < FN; ++ni) {
+          const int row = wn + ni * 16 + fi;
+          bv[ni] = *reinterpret_cast<const bf16x8*>(
+              lb + s * SLAB_B + glds_swz((unsigned)(row * 64 + kb)));
+        }
+#pragma unroll
+        for (int mi = 0; mi < FM; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < FN; ++ni)
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                av[mi], bv[ni], acc[mi][ni], 0, 0, 0);
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+
+    // epilogue of this column tile: bias, one rounding, per-wave transpose,
+    // 16-B nontemporal stores (8 lanes per 128-B line of bf16)
+    float bv4[FN] = {0.f, 0.f, 0.f, 0.f};
+    if (bias) {  // one branch around all four loads, one wait for them
+#pragma unroll
+      for (int ni = 0; ni < FN; ++ni)
+        bv4[ni] = bias[n0 + wn + ni * 16 + fcol];
+    }
+    constexpr int CPR = BNW / 8;                     // 16-B chunks per row
+#pragma unroll
+    for (int mi = 0; mi < FM; ++mi) {
+#pragma unroll
+      for (int ni = 0; ni < FN; ++ni)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = acc[mi][ni][r];
+          if (bias) v += bv4[ni];
+          scratch[(frow + r) * SW + ni * 16 + fcol] = (__bf16)v;
+        }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int it = 0; it < 16 * CPR / PERTGNN_WAVE; ++it) {
+        const int chunk = it * PERTGNN_WAVE + lane;
+        const int r = chunk / CPR;
+        const int off = (chunk % CPR) * 8;
+        const u32x4_t val =
+            *reinterpret_cast<const u32x4_t*>(&scratch[r * SW + off]);
+        const int grow = m0 + wm + mi * 16 + r;
+        if (grow >= m) continue;  // edge tile: rows past the tensor
+        u32x4_t* dst =
+            reinterpret_cast<u32x4_t*>(&c[(long)grow * n + n0 + wn + off]);
+        if constexpr (NTC)
+          __builtin_nontemporal_store(val, dst);
+        else
+          *dst = val;
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+  }
+}
+
 // fp32 [n][k] row-major -> bf16 [n][k] (weight operand for the glds path)
 __global__ void convert_w16_kernel(const float* __restrict__ w,
                                    __bf16* __restrict__ o, long numel) {
@@ -1259,6 +1444,47 @@ void launch_gemm_a16_glds_nt(const void* a_v, const void* b16_v,
     }
 #undef GLDS_DISPATCH
   }
+}
+
+// Forward variant (streaming / A-resident glds NT kernel) as it runs in this
+// process: gemm_dispatch::fwd_variant() under the set_fwd_variant() test hook
+// and PERTGNN_NO_FWD_RESIDENT (read per call, so one process can run both).
+static int g_fwd_variant = gemm_dispatch::FWD_AUTO;  // test hook
+void set_fwd_variant_hook(int v) { g_fwd_variant = v; }
+
+int fwd_variant_for(int m, int n, int k) {
+  const char* e = getenv("PERTGNN_NO_FWD_RESIDENT");
+  return gemm_dispatch::fwd_variant(m, n, k, g_fwd_variant,
+                                    e && e[0] == '1');
+}
+
+// Geometry of the A-resident kernel: 1 = 128-row tiles, 512 threads, B stages
+// of 128 k, one block per CU; 2 = 64-row tiles, 256 threads, B stages of 64 k,
+// two blocks per CU.  PERTGNN_FWD_RES_GEOM (read per call) picks one for the
+// micro-benchmarks; the default is the one that measured faster at the
+// flagship shape (profiles/25_fwd_resident.md).
+static int fwd_resident_geom() {
+  const char* e = getenv("PERTGNN_FWD_RES_GEOM");
+  const int g = e ? atoi(e) : 0;
+  return (g == 1 || g == 2) ? g : gemm_dispatch::FWD_RESIDENT_GEOM;
+}
+
+void launch_gemm_a16_resident_nt(const void* a_v, const void* b16_v,
+                                 const float* bias, void* c_v, int m, int n,
+                                 int k, hipStream_t s) {
+  if (m <= 0) return;
+  const __bf16* a = (const __bf16*)a_v;
+  const __bf16* b = (const __bf16*)b16_v;
+  __bf16* c = (__bf16*)c_v;
+  if (!gemm_dispatch::fwd_resident_can(m, n, k))
+    pertgnn_shape_fail("launch_gemm_a16_resident_nt", k != 256 ? "k" : "n",
+                       k != 256 ? k : n);
+  if (fwd_resident_geom() == 1)
+    gemm_a16_resident_nt_kernel<128, 256, 128, true>
+        <<<dim3((m + 127) / 128), dim3(512), 0, s>>>(a, b, bias, c, m, n);
+  else
+    gemm_a16_resident_nt_kernel<64, 256, 64, true>
+        <<<dim3((m + 63) / 64), dim3(256), 0, s>>>(a, b, bias, c, m, n);
 }
 
 // ---------------------------------------------------------------------------

@@ -58,6 +58,51 @@ inline bool glds_nt_wide(int m, int cols, int contract) {
   return m / 128 >= 1024 && cols == 256 && contract % 32 == 0;
 }
 
+// Forward on the glds NT family: the streaming kernel (every block stages its
+// own A and W K-tiles) or the A-resident kernel (one block keeps a row tile
+// of A in LDS and sweeps the column tiles).  Both give the same bits, so
+// linear_path() reports the family ("glds_nt_128x128") for either.
+enum FwdVariant { FWD_AUTO = 0, FWD_STREAM = 1, FWD_RESIDENT = 2 };
+
+// shapes the two kernels can run at all (a forced variant takes any of them)
+inline bool fwd_stream_can(int m, int n, int k) {
+  return m >= 1 && n % 128 == 0 && k % 32 == 0;
+}
+inline bool fwd_resident_can(int m, int n, int k) {
+  return m >= 1 && n % 128 == 0 && k == 256;
+}
+
+// Geometry the A-resident kernel runs by default (1: 128-row tiles, one
+// block per CU; 2: 64-row tiles, two blocks per CU) and the row count from
+// which it takes over from the streaming kernel.  Measured at n = 1024,
+// k = 256, us per call, streaming / geometry 1 / geometry 2
+// (profiles/25_fwd_resident.md): 16 384 rows 22.7 / 25.9 / 29.3, 45 056
+// 47.8 / 51.1 / 50.0, 57 344 62.3 / 53.6 / 58.1, 65 536 72.6 / 56.6 / 61.5,
+// 73 728 74.5 / 73.6 / 73.3, 90 112 92.3 / 77.5 / 84.4, 180 762 181.5 /
+// 150.2 / 158.1.  Geometry 1 wins from 57 344 rows (448 row tiles) on and
+// loses at 45 056 and below, where its grid is under two blocks per CU.
+constexpr int FWD_RESIDENT_GEOM = 1;
+constexpr int FWD_RESIDENT_MIN_M = 57344;
+
+// the A-resident kernel by default: the k == 256 forward from
+// FWD_RESIDENT_MIN_M rows on, except where the 128x256 tile already streams
+// A once (n == 256 at >= 1024 row tiles)
+inline bool fwd_resident_ok(int m, int n, int k) {
+  return fwd_glds_ok(m, n, k) && fwd_resident_can(m, n, k) &&
+         m >= FWD_RESIDENT_MIN_M && !glds_nt_wide(m, n, k);
+}
+
+// -> FWD_STREAM, FWD_RESIDENT, or 0 where the shape is not on the glds
+// forward.  `forced` (the set_fwd_variant() hook) names the kernel to take
+// on every shape the A-resident kernel can run, rows below the glds gate
+// included, so that the two can be compared there; on any other shape the
+// automatic choice holds.  `no_resident` is PERTGNN_NO_FWD_RESIDENT=1.
+inline int fwd_variant(int m, int n, int k, int forced, bool no_resident) {
+  if (forced != FWD_AUTO && fwd_resident_can(m, n, k)) return forced;
+  if (!fwd_glds_ok(m, n, k)) return 0;
+  return fwd_resident_ok(m, n, k) && !no_resident ? FWD_RESIDENT : FWD_STREAM;
+}
+
 // split-K slice count of the glds TN kernel (K steps of 64 rows; the m % 64
 // tail rides the last non-empty slice and does not change the split)
 inline int glds_tn_slices(int m, int tiles) {
