@@ -188,6 +188,10 @@ void launch_adam(float*, const float*, float*, float*, float*, long, float,
 void launch_adam_dynamic(float*, const float*, float*, float*, float*, float*,
                          long, float, float, float, float, float, float,
                          float, hipStream_t);
+void launch_adam_ex(float*, const float*, float*, float*, float*, float*,
+                    float*, float*, int, const unsigned char*, const float*,
+                    long, long, float, float, float, float, float, float,
+                    float, float, float, float, hipStream_t);
 void launch_gemm_f32_nt(const float*, const float*, const float*, float*, int,
                         int, int, bool, hipStream_t);
 void launch_gemm_f32_nn(const float*, const float*, const float*, float*, int,
@@ -592,6 +596,62 @@ void adam_step_dynamic(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                       p.numel(), (float)lr, (float)b1, (float)b2, (float)eps,
                       (float)backoff, (float)growth, (float)growth_interval,
                       cur_stream());
+}
+
+// Extended Adam step: global-norm clipping (max_norm = inf: none), decoupled
+// weight decay where decay_mask (uint8 per element) is set, and the learning
+// rate of step t from lr_table[min(t, T) - 1].  hstate (8 floats) receives
+// the rate, the clip coefficient and the norm statistics; slab is scratch
+// for the norm's per-block partial sums.  sstate switches on the dynamic
+// loss scaler as in adam_step_dynamic; without it gscale unscales.
+void adam_step_ex(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                  torch::Tensor v, torch::Tensor state, OptTensor sstate,
+                  torch::Tensor hstate, torch::Tensor slab,
+                  OptTensor decay_mask, OptTensor lr_table, double lr,
+                  double b1, double b2, double eps, double gscale, double wd,
+                  double max_norm, double backoff, double growth,
+                  double interval) {
+  CHECK_IN(p); CHECK_IN(g); CHECK_IN(m); CHECK_IN(v); CHECK_IN(state);
+  CHECK_IN(hstate); CHECK_IN(slab);
+  const long numel = p.numel();
+  TORCH_CHECK(g.numel() == numel && m.numel() == numel && v.numel() == numel,
+              "p, g, m and v must have the same number of elements");
+  TORCH_CHECK(state.numel() >= 3, "adam state needs 3 elements");
+  TORCH_CHECK(hstate.numel() >= 8, "hstate needs 8 elements");
+  TORCH_CHECK(slab.numel() >= 1, "slab needs at least 1 element");
+  TORCH_CHECK(!(max_norm < 0.0) && max_norm == max_norm,
+              "max_norm must be non-negative");
+  float* ss = nullptr;
+  if (sstate.has_value()) {
+    CHECK_IN(*sstate);
+    TORCH_CHECK(sstate->numel() >= 3, "scaler state needs 3 elements");
+    ss = sstate->data_ptr<float>();
+  }
+  const unsigned char* mask = nullptr;
+  if (decay_mask.has_value()) {
+    CHECK_IN(*decay_mask);
+    TORCH_CHECK(decay_mask->scalar_type() == torch::kUInt8 &&
+                    decay_mask->numel() == numel,
+                "decay_mask must be uint8 with one entry per element");
+    mask = decay_mask->data_ptr<unsigned char>();
+  }
+  const float* table = nullptr;
+  long table_len = 0;
+  if (lr_table.has_value()) {
+    CHECK_IN(*lr_table);
+    table_len = lr_table->numel();
+    TORCH_CHECK(table_len >= 1, "lr_table must not be empty");
+    table = lr_table->data_ptr<float>();
+  }
+  launch_adam_ex(p.data_ptr<float>(), g.data_ptr<float>(),
+                 m.data_ptr<float>(), v.data_ptr<float>(),
+                 state.data_ptr<float>(), ss, hstate.data_ptr<float>(),
+                 slab.data_ptr<float>(),
+                 (int)std::min<long>(slab.numel(), 4096), mask, table,
+                 table_len, numel, (float)lr, (float)b1, (float)b2,
+                 (float)eps, (float)gscale, (float)wd, (float)max_norm,
+                 (float)backoff, (float)growth, (float)interval,
+                 cur_stream());
 }
 
 // y = x @ w^T + b (torch Linear layout: w [out,in]); bf16 variant rounds
@@ -2409,4 +2469,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("adam_step", &adam_step, py::arg("p"), py::arg("g"), py::arg("m"),
           py::arg("v"), py::arg("state"), py::arg("lr"), py::arg("b1"),
           py::arg("b2"), py::arg("eps"), py::arg("gscale") = 1.0);
+  mod.def("adam_step_ex", &adam_step_ex, py::arg("p"), py::arg("g"),
+          py::arg("m"), py::arg("v"), py::arg("state"), py::arg("sstate"),
+          py::arg("hstate"), py::arg("slab"), py::arg("decay_mask"),
+          py::arg("lr_table"), py::arg("lr"), py::arg("b1"), py::arg("b2"),
+          py::arg("eps"), py::arg("gscale"), py::arg("wd"),
+          py::arg("max_norm"), py::arg("backoff"), py::arg("growth"),
+          py::arg("interval"));
 }

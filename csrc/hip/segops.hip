@@ -2638,3 +2638,181 @@ void launch_adam_dynamic(float* p, const float* g, float* m, float* v,
                                               b1, b2, eps, 1.f, sstate);
   scaler_update_kernel<<<1, 1, 0, s>>>(sstate, backoff, growth, interval);
 }
+
+// ---------------------------------------------------------------------------
+// Extended Adam: global-norm clipping, decoupled weight decay and a learning-
+// rate table, all driven from device state so a captured step replays with
+// the rate and the clip coefficient evolving.  The plain path above is left
+// alone; this one is taken only when one of the three is on.
+//   hstate[0] = learning rate of this step
+//   hstate[1] = clip coefficient of this step (1 when clipping is off)
+//   hstate[2] = gradient norm of this step
+//   hstate[3] = sum of the norms over applied steps since the last reset
+//   hstate[4] = maximum norm since the last reset
+//   hstate[5] = number of clipped steps (coefficient < 1)
+//   hstate[6] = number of applied steps
+//   hstate[7] = spare
+// The norm is a two-level fixed-order reduction (per lane, wave, LDS, then
+// one block over the per-block slab in fp64): no atomics, no memset, and the
+// same bits on every run.
+// ---------------------------------------------------------------------------
+
+// slab[blockIdx.x] = sum of (g[i] * gs)^2 over this block's grid-stride share.
+// g is split by the launcher into `head` scalars up to the first 16-byte
+// boundary, `nvec` float4 and `tail` scalars, so any 4-byte-aligned pointer
+// and any numel work; head and tail (at most 3 each) go to the first lanes
+// of block 0.
+__global__ void grad_sumsq_partial_kernel(const float* __restrict__ g,
+                                          int head, long nvec, int tail,
+                                          float gscale,
+                                          const float* __restrict__ sstate,
+                                          float* __restrict__ slab) {
+  __shared__ float wsum[4];
+  const float gs = sstate ? 1.f / sstate[0] : gscale;
+  const float4* __restrict__ g4 = (const float4*)(g + head);
+  const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  float acc = 0.f;
+  for (long t = i0; t < nvec; t += stride) {
+    const float4 x = g4[t];
+    const float a = x.x * gs, b = x.y * gs, c = x.z * gs, d = x.w * gs;
+    acc += a * a;
+    acc += b * b;
+    acc += c * c;
+    acc += d * d;
+  }
+  if (i0 < head) {
+    const float a = g[i0] * gs;
+    acc += a * a;
+  }
+  if (i0 < tail) {
+    const float a = g[head + 4 * nvec + i0] * gs;
+    acc += a * a;
+  }
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    slab[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// One block: folds the slab in fp64 in a fixed order, then writes the norm,
+// torch.nn.utils.clip_grad_norm_'s coefficient and the running statistics.
+// A skipped step of the dynamic scaler leaves hstate untouched.
+__global__ void grad_norm_fold_kernel(const float* __restrict__ slab, int n,
+                                      float max_norm,
+                                      const float* __restrict__ sstate,
+                                      float* __restrict__ hstate) {
+  __shared__ double part[256];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) acc += (double)slab[i];
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  if (sstate && sstate[2] != 0.f) return;  // skipped step
+  const float norm = (float)sqrt(part[0]);
+  float coef = 1.f;
+  if (!isinf(max_norm)) {
+    const float c = max_norm / (norm + 1e-6f);
+    coef = c > 1.f ? 1.f : c;  // a NaN norm stays NaN, as torch's clamp does
+  }
+  hstate[1] = coef;
+  hstate[2] = norm;
+  hstate[3] += norm;
+  hstate[4] = fmaxf(hstate[4], norm);
+  if (coef < 1.f) hstate[5] += 1.f;
+  hstate[6] += 1.f;
+}
+
+// adam_tick_kernel, and the learning rate of the new step t into hstate[0]:
+// lr_table[min(t, T) - 1] with a table, the by-value lr without one.
+__global__ void adam_tick_ex_kernel(float* __restrict__ state, float b1,
+                                    float b2, const float* __restrict__ sstate,
+                                    float* __restrict__ hstate,
+                                    const float* __restrict__ lr_table,
+                                    long table_len, float lr) {
+  if (sstate && sstate[2] != 0.f) return;  // skipped step
+  const float t = state[0] + 1.f;
+  state[0] = t;
+  state[1] = 1.f - powf(b1, t);
+  state[2] = 1.f - powf(b2, t);
+  if (lr_table) {
+    const long k = (long)t < table_len ? (long)t : table_len;
+    lr = lr_table[k - 1];
+  }
+  hstate[0] = lr;
+}
+
+// adam_kernel's expressions with lr and the clip coefficient read from
+// hstate and torch.optim.AdamW's decoupled decay, p *= 1 - lr * wd, before
+// the moment update wherever decay_mask is set (null when wd == 0).
+__global__ void adam_ex_kernel(float* __restrict__ p,
+                               const float* __restrict__ g,
+                               float* __restrict__ m, float* __restrict__ v,
+                               const float* __restrict__ state,
+                               const float* __restrict__ hstate,
+                               const unsigned char* __restrict__ decay_mask,
+                               long numel, float b1, float b2, float eps,
+                               float gscale, float wd,
+                               const float* __restrict__ sstate) {
+  if (sstate && sstate[2] != 0.f) return;  // skipped step
+  const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const float lr = hstate[0];
+  const float coef = hstate[1];
+  const float step_size = lr / state[1];
+  const float sqrt_bias2 = sqrtf(state[2]);
+  const float gs = sstate ? 1.f / sstate[0] : gscale;
+  const float keep = 1.f - lr * wd;
+  for (long t = i0; t < numel; t += stride) {
+    const float gt = (g[t] * gs) * coef;  // unscale, then clip
+    float pt = p[t];
+    // rounded on its own, so the update below is adam_kernel's to the bit
+    if (decay_mask && decay_mask[t]) pt = __fmul_rn(pt, keep);
+    const float mt = b1 * m[t] + (1.f - b1) * gt;
+    const float vt = b2 * v[t] + (1.f - b2) * gt * gt;
+    m[t] = mt;
+    v[t] = vt;
+    const float denom = sqrtf(vt) / sqrt_bias2 + eps;
+    p[t] = pt - step_size * mt / denom;
+  }
+}
+
+// sstate null: static scaling by gscale; otherwise the dynamic scaler's
+// begin / scan / update kernels wrap the step exactly as in
+// launch_adam_dynamic.  slab holds slab_len >= 1 floats; the partial grid
+// never exceeds it.  Everything is a launch on s: no host read, no copy.
+void launch_adam_ex(float* p, const float* g, float* m, float* v,
+                    float* state, float* sstate, float* hstate, float* slab,
+                    int slab_len, const unsigned char* decay_mask,
+                    const float* lr_table, long table_len, long numel,
+                    float lr, float b1, float b2, float eps, float gscale,
+                    float wd, float max_norm, float backoff, float growth,
+                    float interval, hipStream_t s) {
+  if (numel == 0) return;
+  if (sstate) {
+    scaler_begin_kernel<<<1, 1, 0, s>>>(sstate);
+    grad_scan_kernel<<<grid_for(numel), 256, 0, s>>>(g, numel, sstate);
+  }
+  const long mis = (long)(((uintptr_t)g & 15) / 4);
+  const int head = (int)min((4 - mis) & 3, numel);
+  const long nvec = (numel - head) / 4;
+  const int tail = (int)(numel - head - 4 * nvec);
+  const int grid = min(max(grid_for(nvec), 1), slab_len);
+  grad_sumsq_partial_kernel<<<grid, 256, 0, s>>>(g, head, nvec, tail, gscale,
+                                                 sstate, slab);
+  grad_norm_fold_kernel<<<1, 256, 0, s>>>(slab, grid, max_norm, sstate,
+                                          hstate);
+  adam_tick_ex_kernel<<<1, 1, 0, s>>>(state, b1, b2, sstate, hstate, lr_table,
+                                      table_len, lr);
+  adam_ex_kernel<<<grid_for(numel), 256, 0, s>>>(p, g, m, v, state, hstate,
+                                                 decay_mask, numel, b1, b2,
+                                                 eps, sstate ? 1.f : gscale,
+                                                 wd, sstate);
+  if (sstate)
+    scaler_update_kernel<<<1, 1, 0, s>>>(sstate, backoff, growth, interval);
+}

@@ -19,7 +19,8 @@ from pertgnn.data.collate import BatchLoader
 from pertgnn.data.dataset import build_data_list, split_60_20_20
 from pertgnn.models import SAGEDeterministic
 from pertgnn.parallel import Comm
-from pertgnn.train.optim import FlatGradAllReduce, FusedAdam
+from pertgnn.train.optim import (FlatGradAllReduce, FusedAdam,
+                                 decay_params_of, make_lr_table)
 from pertgnn.train import evaluate, load_checkpoint, save_checkpoint, train_epoch
 from pertgnn.train.checkpoint import check_heads, check_taus
 from pertgnn.utils import JsonlLogger
@@ -108,7 +109,29 @@ def build_parser():
                              "path (pertgnn.infer.Predictor, refreshed after "
                              "every training epoch; captured once over the "
                              "resident eval batches under --hipgraph)")
+    parser.add_argument("--weight_decay", type=float, default=0.0,
+                        help="decoupled (AdamW) weight decay on the weight "
+                             "matrices; embedding tables, BatchNorm affines "
+                             "and biases are never decayed")
+    parser.add_argument("--clip_grad_norm", type=float, default=None,
+                        metavar="N",
+                        help="clip the global gradient norm to N (off by "
+                             "default)")
+    parser.add_argument("--lr_schedule", default="constant",
+                        choices=["constant", "linear", "cosine"],
+                        help="learning-rate schedule over epochs x batches "
+                             "per epoch steps, from --lr down to --min_lr")
+    parser.add_argument("--warmup_steps", type=int, default=0,
+                        help="linear warm-up from 0 to --lr over this many "
+                             "steps")
+    parser.add_argument("--min_lr", type=float, default=0.0,
+                        help="final rate of the linear and cosine schedules")
     return parser
+
+
+# the optimizer flags and the value that leaves each of them off
+OPTIM_FLAGS = {"weight_decay": 0.0, "clip_grad_norm": None,
+               "lr_schedule": "constant", "warmup_steps": 0, "min_lr": 0.0}
 
 
 def parse_args(argv=None):
@@ -128,6 +151,13 @@ def parse_args(argv=None):
         args.tau, args.levels = args.levels[0], None
     if args.tau is None:
         args.tau = 0.5
+    if args.weight_decay < 0:
+        parser.error("--weight_decay must be non-negative")
+    if args.clip_grad_norm is not None and not args.clip_grad_norm > 0:
+        parser.error("--clip_grad_norm must be positive")
+    if args.warmup_steps < 0:
+        parser.error("--warmup_steps must be non-negative")
+    args.optim_ext = any(getattr(args, k) != v for k, v in OPTIM_FLAGS.items())
     return args
 
 
@@ -224,6 +254,11 @@ def main(argv=None):
     args = parse_args(argv)
     shown = argparse.Namespace(**vars(args))
     del shown.levels, shown.levels_given
+    if not args.optim_ext:
+        # a run without the optimizer flags prints the line it always did
+        for k in OPTIM_FLAGS:
+            delattr(shown, k)
+    del shown.optim_ext
     if shown.taus is None:
         del shown.taus  # a run without --taus prints the line it always did
     print(shown)
@@ -334,9 +369,22 @@ def main(argv=None):
     dynamic_scale = str(args.loss_scale).lower() == "dynamic"
     static_scale = 1.0 if dynamic_scale else float(args.loss_scale)
     args.loss_scale = static_scale  # loops use optimizer.scale_loss anyway
+    lr_table = None
+    if args.optim_ext:
+        # one step per training batch of this rank: the count the epoch
+        # loop runs (the resident batches of --hipgraph are cut the same way)
+        total_steps = max(args.epochs * len(train_loader), 1)
+        lr_table = make_lr_table(
+            args.lr, total_steps, args.lr_schedule,
+            warmup_steps=min(args.warmup_steps, total_steps),
+            min_lr=args.min_lr)
     optimizer = FusedAdam(model.parameters(), lr=args.lr,
                           grad_scale=static_scale,
-                          dynamic_scale=dynamic_scale)
+                          dynamic_scale=dynamic_scale,
+                          weight_decay=args.weight_decay,
+                          decay_filter=decay_params_of(model),
+                          max_grad_norm=args.clip_grad_norm,
+                          lr_schedule=lr_table)
     engine = FlatGradAllReduce(optimizer, comm) if comm.distributed else None
     log = JsonlLogger(args.metrics_jsonl, rank=comm.rank)
 
@@ -409,12 +457,15 @@ def main(argv=None):
             if comm.distributed:
                 ql = [comm.all_reduce_scalar(v) for v in ql]
             epoch_stats["q_loss"] = [v / max(n, 1) for v in ql]
+        if stepper.last_grad_stats is not None:
+            epoch_stats["grad_stats"] = stepper.last_grad_stats
         n = max(n, 1)
         return loss_sum / n, mape_sum / n
 
     for epoch in range(start_epoch, args.epochs + 1):
         epoch_stats: dict = {}
         train_mae, train_mape = run_train_epoch(epoch_stats)
+        grad_stats = epoch_stats.pop("grad_stats", None)
         if predictor is not None:
             predictor.refresh()  # the epoch above changed the weights
         valid_rep = evaluate(
@@ -453,6 +504,17 @@ def main(argv=None):
                 "test_coverage": test_rep.coverage,
                 "valid_crossing": valid_rep.crossing,
                 "test_crossing": test_rep.crossing,
+            })
+        if grad_stats is not None:
+            log.print0(
+                f"  lr={grad_stats['lr']}, grad norm mean="
+                f"{grad_stats['norm_mean']}, max={grad_stats['norm_max']}, "
+                f"clipped={100.0 * grad_stats['clipped_frac']}%")
+            record.update({
+                "lr": grad_stats["lr"],
+                "grad_norm_mean": grad_stats["norm_mean"],
+                "grad_norm_max": grad_stats["norm_max"],
+                "clipped_frac": grad_stats["clipped_frac"],
             })
         log.log(record)
         if args.checkpoint and epoch % args.checkpoint_every == 0:

@@ -48,6 +48,8 @@ class GraphStepper:
         self.levels = None if F._is_level(tau) else ref.check_taus(tau)
         self.point = ref.point_level(self.levels) if self.levels else 0
         self.last_q_loss = None  # per-level averages of the last epoch
+        # FusedAdam.grad_stats() of the last epoch (extended step only)
+        self.last_grad_stats = None
         self.acc = torch.zeros(2 + (len(self.levels) if self.levels else 0),
                                dtype=torch.float32,
                                device=device if self.on_gpu else "cpu")
@@ -103,6 +105,10 @@ class GraphStepper:
             "dev_state": opt.dev_state.detach().clone(),
             "sstate": (opt.sstate.detach().clone()
                        if getattr(opt, "sstate", None) is not None else None),
+            # learning rate, clip coefficient and norm statistics: the
+            # warmup steps walked the schedule and counted themselves
+            "hstate": (opt.hstate.detach().clone()
+                       if getattr(opt, "hstate", None) is not None else None),
             "step_count": opt.step_count,
             "buffers": [(b, b.detach().clone()) for b in self.model.buffers()
                         if torch.is_tensor(b) and b.numel() > 0],
@@ -118,6 +124,8 @@ class GraphStepper:
             opt.dev_state.copy_(snap["dev_state"])
             if snap["sstate"] is not None:
                 opt.sstate.copy_(snap["sstate"])
+            if snap["hstate"] is not None:
+                opt.hstate.copy_(snap["hstate"])
             opt.step_count = snap["step_count"]
             for b, saved in snap["buffers"]:
                 b.copy_(saved)
@@ -195,6 +203,8 @@ class GraphStepper:
         if self.on_gpu:
             torch.cuda.synchronize()
         total_loss, mape_sum, *level_sums = self.acc.tolist()
+        if getattr(self.optimizer, "extended", False):
+            self.last_grad_stats = self.optimizer.grad_stats()
         if self.levels is not None:
             # rank-local, like the sums returned
             self.last_q_loss = [v / max(self.n_graphs, 1) for v in level_sums]

@@ -93,7 +93,12 @@ def train_epoch(model, loader, optimizer, tau, device, engine=None, comm=None,
     ``tau`` may be a sequence of Q levels: the model then emits ``[B, Q]``,
     training minimises the pinball loss summed over the levels, avg_loss is
     that sum, avg_mape is of the point level, and ``stats_out["q_loss"]``
-    receives the per-level averages."""
+    receives the per-level averages.
+
+    With FusedAdam's extended step active (clipping, weight decay or a
+    learning-rate table) ``stats_out["grad_stats"]`` receives
+    ``optimizer.grad_stats()`` of the epoch (rank-local; under DDP every
+    rank sees the norm of the same averaged gradient)."""
     import time as _time
 
     levels = _levels(tau)
@@ -151,6 +156,8 @@ def train_epoch(model, loader, optimizer, tau, device, engine=None, comm=None,
     sums = (acc.tolist() if acc is not None
             else [0.0] * (2 + (len(levels) if levels else 0)))
     total_loss, mape_sum, level_sums = sums[0], sums[1], sums[2:]
+    grad_stats = (optimizer.grad_stats()
+                  if getattr(optimizer, "extended", False) else None)
     elapsed = _time.perf_counter() - t0
     if comm is not None and comm.distributed:
         total_loss = comm.all_reduce_scalar(total_loss)
@@ -170,6 +177,8 @@ def train_epoch(model, loader, optimizer, tau, device, engine=None, comm=None,
     n = max(n_graphs, 1)
     if stats_out is not None and levels is not None:
         stats_out["q_loss"] = [v / n for v in level_sums]
+    if stats_out is not None and grad_stats is not None:
+        stats_out["grad_stats"] = grad_stats
     return total_loss / n, mape_sum / n
 
 

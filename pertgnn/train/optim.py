@@ -9,8 +9,19 @@ matching flat buffer (``p.grad`` is pre-set to a view), so:
     (HIP ``adam_step`` on GPU, the same flat math eagerly on CPU);
   * DDP gradient all-reduce operates on slices of the flat grad buffer with
     zero packing copies (see FlatGradAllReduce).
+
+Three optional features take the step onto the extended kernels (HIP
+``adam_step_ex``): global-norm gradient clipping (``max_grad_norm``),
+decoupled weight decay (``weight_decay`` over the parameters ``decay_filter``
+selects, torch.optim.AdamW order) and a per-step learning-rate table
+(``lr_schedule``).  The rate of the step, the clip coefficient and the
+gradient-norm statistics live on the device (``hstate``) next to the step
+counter, so a captured step walks the schedule across replays.  With all
+three off the step is the plain one, call for call.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -24,10 +35,61 @@ def _trainable(params):
     ]
 
 
+def make_lr_table(base_lr, total_steps, kind="constant", warmup_steps=0,
+                  min_lr=0.0):
+    """The learning rate of steps 1..total_steps as an fp32 tensor: linear
+    warm-up ``base * t / W`` for ``t <= W``, then with
+    ``s = (t - W) / (T - W)`` constant ``base``, linear
+    ``base + (min - base) * s`` or cosine
+    ``min + (base - min) * (1 + cos(pi * s)) / 2``.  Computed in fp64 on the
+    host and rounded once."""
+    if kind not in ("constant", "linear", "cosine"):
+        raise ValueError(f"unknown lr schedule {kind!r}")
+    T, W = int(total_steps), int(warmup_steps)
+    if T < 1:
+        raise ValueError("total_steps must be at least 1")
+    if not 0 <= W <= T:
+        raise ValueError("warmup_steps must lie in [0, total_steps]")
+    base, low = float(base_lr), float(min_lr)
+    out = []
+    for t in range(1, T + 1):
+        if t <= W:
+            out.append(base * t / W)
+            continue
+        s = (t - W) / (T - W)
+        if kind == "cosine":
+            out.append(low + (base - low) * 0.5 * (1.0 + math.cos(math.pi * s)))
+        elif kind == "linear":
+            out.append(base + (low - base) * s)
+        else:
+            out.append(base)
+    return torch.tensor(out, dtype=torch.float64).to(torch.float32)
+
+
+def decay_params_of(model):
+    """The ``decay_filter`` the CLI uses: weights of at least 2 dimensions,
+    minus every ``nn.Embedding`` table (category, interface, rpc, entry);
+    BatchNorm affines and biases are 1-D and so never decayed."""
+    skip = set()
+    for mod in model.modules():
+        if isinstance(mod, (torch.nn.Embedding,
+                            torch.nn.modules.batchnorm._BatchNorm)):
+            skip.update(id(p) for p in mod.parameters(recurse=False))
+    keep = {id(p) for p in _trainable(model.parameters())
+            if p.dim() >= 2 and id(p) not in skip}
+    return lambda p: id(p) in keep
+
+
+HSTATE_LEN = 8   # [lr, clip coef, norm, norm sum, norm max, clipped, steps, -]
+SLAB_LEN = 4096  # one partial sum per block of the norm kernel (grid cap)
+
+
 class FusedAdam:
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  grad_scale=1.0, dynamic_scale=False, init_scale=2.0 ** 16,
-                 growth_interval=2000, backoff=0.5, growth=2.0):
+                 growth_interval=2000, backoff=0.5, growth=2.0,
+                 weight_decay=0.0, decay_filter=None, max_grad_norm=None,
+                 lr_schedule=None):
         self.params = _trainable(list(params))
         assert self.params, "no trainable parameters"
         assert all(p.dtype == torch.float32 for p in self.params), "fp32 master params only"
@@ -71,6 +133,37 @@ class FusedAdam:
             self._pin_grad(p, off)
             off += n
 
+        self.weight_decay = float(weight_decay)
+        self.max_grad_norm = (None if max_grad_norm is None
+                              else float(max_grad_norm))
+        if self.weight_decay < 0.0:
+            raise ValueError("weight_decay must be non-negative")
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0.0:
+            raise ValueError("max_grad_norm must be positive")
+        self.lr_table = None
+        if lr_schedule is not None:
+            table = torch.as_tensor(lr_schedule, dtype=torch.float32)
+            if table.dim() != 1 or table.numel() == 0:
+                raise ValueError("lr_schedule must be a non-empty 1-D sequence")
+            self.lr_table = table.detach().clone().contiguous().to(device)
+        self.decay_mask = None
+        if self.weight_decay != 0.0:
+            keep = decay_filter or (lambda p: p.dim() >= 2)
+            # built once: one uint8 per element of the flat buffers
+            self.decay_mask = torch.cat([
+                torch.full((p.numel(),), 1 if keep(p) else 0, dtype=torch.uint8)
+                for p in self.params]).to(device)
+        # the extended step: taken only when a feature is on
+        self.extended = (self.weight_decay != 0.0
+                         or self.max_grad_norm is not None
+                         or self.lr_table is not None)
+        # device-side [lr, clip coef, norm, norm sum, norm max, clipped
+        # steps, applied steps, spare]; slab is the norm kernel's scratch
+        self.hstate = torch.zeros(HSTATE_LEN, dtype=torch.float32, device=device)
+        self.hstate[1] = 1.0
+        self.slab = (torch.zeros(SLAB_LEN, dtype=torch.float32, device=device)
+                     if self.extended else None)
+
     def _pin_grad(self, p, off):
         """Point ``p.grad`` at its ``flat_grad`` slice and record that slice
         as the parameter's gradient sink: the native backward ops add a
@@ -102,7 +195,17 @@ class FusedAdam:
         b1, b2 = self.betas
         if self.flat_param.is_cuda and has_hip():
             self.step_count += 1
-            if self.dynamic_scale:
+            if self.extended:
+                ext().adam_step_ex(
+                    self.flat_param, self.flat_grad, self.exp_avg,
+                    self.exp_avg_sq, self.dev_state, self.sstate, self.hstate,
+                    self.slab, self.decay_mask, self.lr_table, self.lr,
+                    b1, b2, self.eps, 1.0 / self.grad_scale,
+                    self.weight_decay,
+                    math.inf if self.max_grad_norm is None
+                    else self.max_grad_norm,
+                    self.backoff, self.growth, self.growth_interval)
+            elif self.dynamic_scale:
                 ext().adam_step_dynamic(
                     self.flat_param, self.flat_grad, self.exp_avg,
                     self.exp_avg_sq, self.dev_state, self.sstate, self.lr,
@@ -128,6 +231,9 @@ class FusedAdam:
                 self.sstate[1] = 0.0
         else:
             inv = 1.0 / self.grad_scale
+        if self.extended:
+            self._eager_step_ex(g, inv)
+            return
         self.step_count += 1
         self.exp_avg.mul_(b1).add_(g, alpha=(1 - b1) * inv)
         self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=(1 - b2) * inv * inv)
@@ -135,6 +241,60 @@ class FusedAdam:
         bias2 = 1 - b2 ** self.step_count
         denom = (self.exp_avg_sq.sqrt() / (bias2 ** 0.5)).add_(self.eps)
         self.flat_param.addcdiv_(self.exp_avg, denom, value=-self.lr / bias1)
+
+    def _eager_step_ex(self, g, inv):
+        """The extended step, eagerly: unscale, norm, clip, the rate of the
+        new applied-step count, decoupled decay, Adam."""
+        b1, b2 = self.betas
+        h = self.hstate
+        g = g * inv
+        norm = torch.linalg.vector_norm(g)
+        coef = torch.ones((), dtype=torch.float32, device=g.device)
+        if self.max_grad_norm is not None:
+            coef = torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0)
+        self.step_count += 1
+        t = self.step_count
+        lr = self.lr
+        if self.lr_table is not None:
+            lr = float(self.lr_table[min(t, self.lr_table.numel()) - 1])
+        h[0] = lr
+        h[1] = coef
+        h[2] = norm
+        h[3] += norm
+        h[4] = torch.maximum(h[4], norm)
+        if bool(coef < 1.0):
+            h[5] += 1.0
+        h[6] += 1.0
+        lr = float(h[0])  # the fp32 rate, as the kernel reads it
+        g = g * coef
+        if self.decay_mask is not None:
+            keep = torch.where(self.decay_mask.bool(),
+                               1.0 - lr * self.weight_decay, 1.0)
+            self.flat_param.mul_(keep.to(torch.float32))
+        self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
+        self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
+        bias1 = 1 - b1 ** t
+        bias2 = 1 - b2 ** t
+        denom = (self.exp_avg_sq.sqrt() / (bias2 ** 0.5)).add_(self.eps)
+        self.flat_param.addcdiv_(self.exp_avg, denom, value=-lr / bias1)
+
+    def grad_stats(self, reset=True):
+        """Learning rate and gradient-norm statistics of the extended step
+        since the last reset, from ONE read of the device state: ``lr`` and
+        ``norm_last`` of the latest applied step, ``norm_mean`` / ``norm_max``
+        over the applied steps, the fraction of them that were clipped, and
+        their count.  ``reset`` zeroes the running statistics."""
+        lr, _coef, last, total, peak, clipped, steps, _ = self.hstate.tolist()
+        if reset:
+            self.hstate[3:7].zero_()
+        return {
+            "lr": lr,
+            "norm_last": last,
+            "norm_mean": total / steps if steps else 0.0,
+            "norm_max": peak,
+            "clipped_frac": clipped / steps if steps else 0.0,
+            "steps": int(steps),
+        }
 
     def _synced_step_count(self) -> int:
         """True step count on GPU: the device-side counter is authoritative —
@@ -157,6 +317,9 @@ class FusedAdam:
         }
         if self.sstate is not None:
             sd["sstate"] = self.sstate
+        sd["weight_decay"] = self.weight_decay
+        sd["max_grad_norm"] = self.max_grad_norm
+        sd["hstate"] = self.hstate
         return sd
 
     def load_state_dict(self, sd):
@@ -168,6 +331,11 @@ class FusedAdam:
         self.exp_avg.copy_(sd["exp_avg"].to(self.exp_avg.device))
         self.exp_avg_sq.copy_(sd["exp_avg_sq"].to(self.exp_avg_sq.device))
         self.lr = sd.get("lr", self.lr)
+        # the statistics and the rate last used; weight_decay, max_grad_norm
+        # and the table stay the constructor's (resuming with other flags is
+        # legitimate), the schedule position is dev_state[0]
+        if "hstate" in sd:
+            self.hstate.copy_(sd["hstate"].to(self.hstate.device))
 
 
 class FlatGradAllReduce:
