@@ -11,8 +11,8 @@
 
 #include <c10/cuda/CUDAStream.h>
 
-#include "hip/attn_bn.h"
 #include "hip/gemm_dispatch.h"
+#include "hip/launchers.h"
 
 namespace {
 
@@ -78,228 +78,7 @@ inline BnAffineOut bn_affine_out(const OptTensor& dgamma_sink,
 
 }  // namespace
 
-// launchers (csrc/hip/*.hip)
-void launch_edge_attn_fwd(const float*, const float*, const float*,
-                          const float*, const int*, const int*, const float*,
-                          float*, float*, int, int, hipStream_t);
-void launch_edge_attn_bwd(const float*, const float*, const float*,
-                          const float*, const float*, const float*, const int*,
-                          const int*, const int*, const int*, float*, float*,
-                          float*, float*, float*, float*, int, int, long,
-                          hipStream_t);
-void launch_seg_pool_fwd(const float*, const float*, const float*, const int*,
-                         float*, float*, int, int, int, hipStream_t);
-void launch_seg_pool_bwd(const float*, const float*, const float*, const long*,
-                         float*, long, int, hipStream_t);
-void launch_embed_node_fwd(const float*, const long*, const float*, float*,
-                           long, int, int, hipStream_t);
-void launch_embed_node_fwd16(const float*, const long*, const float*, void*,
-                             long, int, int, hipStream_t);
-void launch_embed_node_pad(const float*, const long*, const float*, void*, int,
-                           long, int, int, int, hipStream_t);
-void launch_vocab_scatter16(const void*, const long*, long, float*, long, int,
-                            int, int, int, hipStream_t);
-void launch_embed_edge_fwd(const long*, const float*, const float*, float*,
-                           long, int, int, hipStream_t);
-void launch_gather_rows(const long*, const float*, float*, long, int,
-                        hipStream_t);
-// wide-load BN path: fast-path shape test, and the per-call slab rows a
-// reduction over [n, h] needs (0 = none); trailing float* = that slab,
-// trailing unsigned char* = bit-packed ReLU keep mask [n, h/8] (or null)
-bool bn_wide_ok(int);
-int bn_wide_slab_rows(long, int);
-void launch_bn_fwd(const float*, const float*, const float*, float*, float*,
-                   float*, float*, float*, float*, long, int, float, float,
-                   bool, bool, float, const unsigned long long*, float*,
-                   hipStream_t);
-void launch_counter_bump(unsigned long long*, hipStream_t);
-void launch_bn_bwd(const float*, const float*, const float*, const float*,
-                   const float*, const float*, float*, float*, float*, float*,
-                   long, int, bool, float, float*, hipStream_t,
-                   bool acc = false);
-void launch_bn_stats_only(const float*, long, int, float*, float*,
-                          hipStream_t);
-void launch_bn_finalize_apply(const float*, const float*, const float*,
-                              const float*, const float*, float*, float*,
-                              float*, float*, float*, long, int, float, float,
-                              bool, bool, float, const unsigned long long*,
-                              hipStream_t);
-void launch_bn_bwd_partials_only(const float*, const float*, const float*,
-                                 const float*, const float*, long, int, bool,
-                                 float*, float, float*, hipStream_t);
-void launch_bn_bwd_apply_only(const float*, const float*, const float*,
-                              const float*, const float*, const float*,
-                              const float*, const float*, float*, long, int,
-                              bool, float, hipStream_t);
-// trailing `bool acc` of a backward launcher: its parameter-gradient outputs
-// are gradient sinks (see grad_sink below), added to and never cleared
-void launch_bn_grad_affine(const float*, float*, float*, int, hipStream_t,
-                           bool acc = false);
-// act16 variants (bf16 x/y/g/dx streams, fp32 statistics)
-void launch_bn_stats_only16(const void*, long, int, float*, float*,
-                            hipStream_t);
-void launch_bn_fwd16(const void*, const float*, const float*, float*, float*,
-                     float*, float*, float*, void*, long, int, float, float,
-                     bool, bool, float, const unsigned long long*, float*,
-                     unsigned char*, hipStream_t);
-void launch_bn_finalize_apply16(const void*, const float*, const float*,
-                                const float*, const float*, float*, float*,
-                                float*, float*, void*, long, int, float, float,
-                                bool, bool, float, const unsigned long long*,
-                                unsigned char*, hipStream_t);
-void launch_bn_bwd_partials_only16(const void*, const void*, const void*,
-                                   const float*, const float*, long, int, bool,
-                                   float*, float, float*,
-                                   const unsigned char*, hipStream_t);
-void launch_bn_bwd_apply_only16(const void*, const void*, const void*,
-                                const float*, const float*, const float*,
-                                const float*, const float*, void*, long, int,
-                                bool, float, const unsigned char*,
-                                hipStream_t);
-void launch_bn_bwd16(const void*, const void*, const void*, const float*,
-                     const float*, const float*, float*, void*, float*,
-                     float*, long, int, bool, float, float*,
-                     const unsigned char*, hipStream_t, bool acc = false);
-void launch_seg_pool_fwd16(const void*, const float*, const float*,
-                           const int*, float*, float*, int, int, int,
-                           hipStream_t);
-void launch_seg_pool_bwd16(const float*, const float*, const float*,
-                           const long*, void*, long, int, hipStream_t);
-void launch_gemm_bf16_nt_a16o16(const void*, const float*, const float*,
-                                void*, int, int, int, hipStream_t);
-void launch_gemm_bf16_nn_a16o16(const void*, const float*, void*, int, int,
-                                int, hipStream_t);
-void launch_gemm_bf16_tn_a16b16(const void*, const void*, float*, float*, int,
-                                int, int, hipStream_t, bool acc = false);
-void launch_gemm_fp16_nt_a16o16(const void*, const float*, const float*,
-                                void*, int, int, int, hipStream_t);
-void launch_gemm_fp16_nn_a16o16(const void*, const float*, void*, int, int,
-                                int, hipStream_t);
-void launch_gemm_fp16_tn_a16b16(const void*, const void*, float*, float*, int,
-                                int, int, hipStream_t, bool acc = false);
-void launch_quantile_loss_fwd(const float*, const float*, float*, long, float,
-                              hipStream_t);
-void launch_quantile_loss_bwd(const float*, const float*, const float*, float*,
-                              long, float, hipStream_t);
-void launch_eval_metrics(const float*, const float*, float*, long, float,
-                         hipStream_t);
-void launch_adam(float*, const float*, float*, float*, float*, long, float,
-                 float, float, float, float, hipStream_t);
-void launch_adam_dynamic(float*, const float*, float*, float*, float*, float*,
-                         long, float, float, float, float, float, float,
-                         float, hipStream_t);
-void launch_adam_ex(float*, const float*, float*, float*, float*, float*,
-                    float*, float*, int, const unsigned char*, const float*,
-                    long, long, float, float, float, float, float, float,
-                    float, float, float, float, hipStream_t);
-void launch_gemm_f32_nt(const float*, const float*, const float*, float*, int,
-                        int, int, bool, hipStream_t);
-void launch_gemm_f32_nn(const float*, const float*, const float*, float*, int,
-                        int, int, bool, hipStream_t);
-void launch_gemm_f32_tn(const float*, const float*, float*, float*, int, int,
-                        int, hipStream_t);
-void launch_colsum(const float*, float*, long, int, hipStream_t);
-void launch_gemm_bf16_nt(const float*, const float*, const float*, float*,
-                         int, int, int, bool, hipStream_t);
-void launch_gemm_bf16_nn(const float*, const float*, const float*, float*,
-                         int, int, int, bool, hipStream_t);
-void launch_gemm_bf16_tn(const float*, const float*, float*, float*, int, int,
-                         int, hipStream_t);
-void launch_gemm_fp16_nt(const float*, const float*, const float*, float*,
-                         int, int, int, bool, hipStream_t);
-void launch_gemm_fp16_nn(const float*, const float*, const float*, float*,
-                         int, int, int, bool, hipStream_t);
-void launch_gemm_fp16_tn(const float*, const float*, float*, float*, int, int,
-                         int, hipStream_t);
-void launch_embed_grouped_scatter(const float*, const int*, const int*, float*,
-                                  float*, long, int, int, int, int, int,
-                                  hipStream_t);
-void launch_embed_grouped_scatter_bal(const void*, int, const int*,
-                                      const int*, const int*, const int*,
-                                      const int*, const int*, float*, float*,
-                                      float*, int, int, int, int, int, int,
-                                      hipStream_t);
-void launch_rows_sum_lists(const void*, int, const int*, const int*, void*, int,
-                           int, int, int, hipStream_t);
-void launch_rows_sum_lists_wide(const void*, int, int, const int*, const int*,
-                                float*, int, int, int, int, int, hipStream_t);
-void launch_embed_fold_gemm(const float*, const float*, float*, int, int, int,
-                            int, int, bool, hipStream_t);
-void launch_vocab_scatter(const float*, const long*, long, float*, long, int,
-                          int, int, int, hipStream_t);
-void launch_vocab_scatter_dual(const float*, const long*, int, float*, float*,
-                               long, int, int, int, hipStream_t);
-void launch_edge_attn_fused_fwd(const float*, const float*, const float*,
-                                const long*, int, const int*, const int*,
-                                float*, float*, int, int, int, hipStream_t);
-void launch_edge_attn_fused_bwd(const float*, const float*, const float*,
-                                const float*, const long*, int, const float*,
-                                const int*, const int*, const int*,
-                                const int*, const int*, float*, float*,
-                                float*, int, int, long, int, hipStream_t);
-void launch_edge_attn_fused_fwd16(const void*, const void*, const void*,
-                                  int, const long*, int, const int*,
-                                  const int*, void*, int, float*, int, int,
-                                  int, hipStream_t);
-void launch_edge_attn_fused_bwd16(const void*, int, const void*,
-                                  const void*, const void*, int, const long*,
-                                  int, const float*, const int*, const int*,
-                                  const int*, const int*, const int*, void*,
-                                  void*, float*, int, int, long, int,
-                                  hipStream_t, const AttnBnBwd* = nullptr,
-                                  const AttnPoolBwd* = nullptr);
-void launch_bn_bwd_partials_affine16(const void*, const void*,
-                                     const unsigned char*, const float*,
-                                     const float*, long, int, float*, float,
-                                     float*, float*, float*, hipStream_t,
-                                     bool acc = false);
-void launch_edge_attn_fused_infer(const float*, const float*, const float*,
-                                  const long*, int, const int*, const int*,
-                                  const float*, const float*, int, float*,
-                                  int, int, int, hipStream_t);
-void launch_edge_attn_fused_infer16(const void*, const void*, const void*,
-                                    int, const long*, int, const int*,
-                                    const int*, const float*, const float*,
-                                    int, void*, int, int, int, int,
-                                    hipStream_t);
-void launch_vocab_scatter_dual16(const void*, const long*, int, float*,
-                                 float*, long, int, int, int, hipStream_t);
-void launch_gemm_bf16_nt_o16(const float*, const float*, const float*, void*,
-                             int, int, int, hipStream_t);
-void launch_gemm_a16_glds_nt(const void*, const void*, const float*, void*,
-                             int, int, int, int, bool, hipStream_t);
-void launch_convert_w16(const float*, void*, long, hipStream_t);
-void launch_convert_w16_both(const float*, void*, void*, int, int,
-                             hipStream_t);
-void launch_gemm_a16_glds_tn(const void*, const void*, float*, float*, int,
-                             int, int, hipStream_t, bool acc = false,
-                             int tile = 0);
-// the tile (gemm_dispatch::TnTile) that launcher runs for a shape it
-// supports: `tile` if forced (-1 where the shape does not allow it), else
-// the process-wide override or the dispatch's choice
-int glds_tn_tile_for(int m, int n, int k2, int tile);
-void launch_gemm_a16_resident_nt(const void*, const void*, const float*, void*,
-                                 int, int, int, hipStream_t);
-int fwd_variant_for(int m, int n, int k);
-void set_fwd_variant_hook(int v);
-void set_glds_tn_tile(int tile);
-void launch_transpose_convert_w16(const float*, void*, int, int, hipStream_t);
-void launch_gemm_skinny_nn(const void*, const float*, float*, int, int, int,
-                           hipStream_t);
-void launch_gemm_bf16_nn_a16(const void*, const float*, float*, int, int, int,
-                             hipStream_t);
-void launch_gemm_bf16_tn_a16(const void*, const float*, float*, float*, int,
-                             int, int, hipStream_t, bool acc = false);
-// grouped P-table GEMMs (all layers, both tables, one launch each)
-int ptables_max_groups();
-void launch_ptables_fwd(int, const float* const*, const float* const*,
-                        void* const*, const int*, int, int, hipStream_t);
-void launch_ptables_dgrad(const void* const*, const float* const*, const int*,
-                          float* const*, const int*, int, int, const bool*,
-                          hipStream_t);
-bool launch_ptables_wgrad(int, const void* const*, const float* const*,
-                          float* const*, const int*, int, bool, hipStream_t,
-                          const bool* sink = nullptr);
+// csrc/collate.cpp
 std::vector<torch::Tensor> collate_native(
     std::vector<torch::Tensor>, std::vector<torch::Tensor>,
     std::vector<torch::Tensor>, std::vector<torch::Tensor>,
@@ -361,16 +140,20 @@ std::vector<torch::Tensor> edge_attn_bwd(
   return {dq, dk, dv, de};
 }
 
+// partial sums per graph of the pattern pool's first pass: about 8192 over
+// the batch, no more than a graph's share of the n rows, 1..64
+static long seg_pool_parts(long n, int64_t num_graphs) {
+  const long graphs = std::max<int64_t>(num_graphs, 1);
+  const long per_g = (n + graphs - 1) / graphs;
+  return std::min<long>(std::max<long>(std::min(8192 / graphs, per_g), 1), 64);
+}
+
 torch::Tensor seg_pool_fwd(torch::Tensor x, torch::Tensor probs,
                            torch::Tensor nn, torch::Tensor batch_ptr,
                            int64_t num_graphs) {
   CHECK_IN(x); CHECK_IN(probs); CHECK_IN(nn); CHECK_IN(batch_ptr);
   const int h = x.size(1);
-  const long n = x.size(0);
-  long p = 8192 / std::max<int64_t>(num_graphs, 1);
-  const long per_g = (n + std::max<int64_t>(num_graphs, 1) - 1) /
-                     std::max<int64_t>(num_graphs, 1);
-  p = std::min<long>(std::max<long>(std::min(p, per_g), 1), 64);
+  const long p = seg_pool_parts(x.size(0), num_graphs);
   auto partial = torch::empty({num_graphs * p, h}, x.options());
   auto out = torch::empty({num_graphs, h}, x.options());
   launch_seg_pool_fwd(x.data_ptr<float>(), probs.data_ptr<float>(),
@@ -489,53 +272,230 @@ static torch::Tensor bn_new_mask(const torch::Tensor& x, bool training,
                       x.options().dtype(torch::kUInt8));
 }
 
+// ---------------------------------------------------------------------------
+// BatchNorm(+ReLU+dropout).  Every operation is one function for both
+// activation dtypes, dispatching on x.scalar_type(): fp32, or bf16 (act16:
+// the x, y, g and dx streams are bf16; statistics, affine parameters and
+// their gradients stay fp32).  It is bound under two Python names that are
+// aliases checking the dtype: the plain one (A16 = false) requires fp32
+// activations, the "16" one bf16.  The bf16 forwards also return the keep
+// mask (empty where none is written), so they return four tensors, the fp32
+// ones three.
+// ---------------------------------------------------------------------------
+
+// The gate of the BN bindings: x is [n, h] of the dtype the name requires; g
+// (a backward's incoming gradient) matches it in dtype and shape; ym is y,
+// or for bf16 the uint8 keep mask that bn_mask_ptr accepts.  -> x is bf16
+static bool bn_gate(const char* name, bool a16, const torch::Tensor& x,
+                    const torch::Tensor* g = nullptr,
+                    const torch::Tensor* ym = nullptr) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2, name,
+              ": x must be a contiguous [n, h] GPU tensor");
+  TORCH_CHECK(x.size(1) <= INT_MAX, name, ": h does not fit an int");
+  TORCH_CHECK(x.scalar_type() == (a16 ? torch::kBFloat16 : torch::kFloat32),
+              name, " takes ", a16 ? "bf16" : "fp32", " activations, got ",
+              x.scalar_type(), a16 ? " (fp32 ones go to the name without 16)"
+                                   : " (bf16 ones go to the name with 16)");
+  if (g)
+    TORCH_CHECK(g->is_cuda() && g->is_contiguous() &&
+                    g->scalar_type() == x.scalar_type() &&
+                    g->sizes() == x.sizes(),
+                name, ": g must match x in dtype and shape, got ",
+                g->scalar_type(), " ", g->sizes(), " for x ", x.sizes());
+  if (ym && !(a16 && ym->scalar_type() == torch::kUInt8))
+    TORCH_CHECK(ym->is_cuda() && ym->is_contiguous() &&
+                    ym->scalar_type() == x.scalar_type() &&
+                    ym->sizes() == x.sizes(),
+                name, ": y must match x in dtype and shape",
+                a16 ? " (or be the uint8 keep mask)" : "");
+  return x.scalar_type() == torch::kBFloat16;
+}
+
+static void bn_partials_check(const char* name, const torch::Tensor& partials,
+                              int h) {
+  TORCH_CHECK(partials.numel() == 2 * h + 1, name,
+              " expects [2h+1] partials with the global count in the tail "
+              "slot");
+}
+
+template <bool A16>
 std::vector<torch::Tensor> bn_relu_fwd(torch::Tensor x, torch::Tensor gamma,
                                        torch::Tensor beta,
                                        torch::Tensor running_mean,
                                        torch::Tensor running_var,
                                        double momentum, double eps,
                                        bool training, bool relu,
-                                       double dropout_p = 0.0,
-                                       torch::Tensor seed = {}) {
-  CHECK_IN(x); CHECK_IN(gamma); CHECK_IN(beta);
+                                       double dropout_p, torch::Tensor seed) {
+  const bool b16 = bn_gate(A16 ? "bn_relu_fwd16" : "bn_relu_fwd", A16, x);
+  CHECK_IN(gamma); CHECK_IN(beta);
   const long n = x.size(0);
   const int h = x.size(1);
+  auto fopt = x.options().dtype(torch::kFloat32);
   auto y = torch::empty_like(x);
-  auto mean = torch::empty({h}, x.options());
-  auto invstd = torch::empty({h}, x.options());
-  auto partials = torch::empty({2 * h}, x.options());
-  auto slab = training ? bn_wide_slab(x) : torch::empty({0}, x.options());
+  auto mean = torch::empty({h}, fopt);
+  auto invstd = torch::empty({h}, fopt);
+  auto partials = torch::empty({2 * h}, fopt);
+  auto slab = training ? bn_wide_slab(x) : torch::empty({0}, fopt);
   const auto* sp = rng_seed_ptr(seed, dropout_p);
-  launch_bn_fwd(x.data_ptr<float>(), gamma.data_ptr<float>(),
-                beta.data_ptr<float>(), running_mean.data_ptr<float>(),
-                running_var.data_ptr<float>(), mean.data_ptr<float>(),
-                invstd.data_ptr<float>(), partials.data_ptr<float>(),
-                y.data_ptr<float>(), n, h, (float)momentum, (float)eps,
-                training, relu, (float)dropout_p, sp, bn_slab_ptr(slab),
-                cur_stream());
+  torch::Tensor mask;
+  if (b16) {
+    mask = bn_new_mask(x, training, relu);
+    launch_bn_fwd16(x.data_ptr(), gamma.data_ptr<float>(),
+                    beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+                    running_var.data_ptr<float>(), mean.data_ptr<float>(),
+                    invstd.data_ptr<float>(), partials.data_ptr<float>(),
+                    y.data_ptr(), n, h, (float)momentum, (float)eps, training,
+                    relu, (float)dropout_p, sp, bn_slab_ptr(slab),
+                    mask.numel() ? mask.data_ptr<unsigned char>() : nullptr,
+                    cur_stream());
+  } else {
+    launch_bn_fwd(x.data_ptr<float>(), gamma.data_ptr<float>(),
+                  beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+                  running_var.data_ptr<float>(), mean.data_ptr<float>(),
+                  invstd.data_ptr<float>(), partials.data_ptr<float>(),
+                  y.data_ptr<float>(), n, h, (float)momentum, (float)eps,
+                  training, relu, (float)dropout_p, sp, bn_slab_ptr(slab),
+                  cur_stream());
+  }
   if (sp) launch_counter_bump((unsigned long long*)seed.data_ptr<long>(),
                               cur_stream());
+  if (b16) return {y, mean, invstd, mask};
   return {y, mean, invstd};
 }
 
+template <bool A16>
 std::vector<torch::Tensor> bn_relu_bwd(torch::Tensor g, torch::Tensor x,
                                        torch::Tensor gamma, torch::Tensor mean,
                                        torch::Tensor invstd, torch::Tensor y,
-                                       bool relu, double keep_inv = 1.0,
-                                       OptTensor dgamma_sink = std::nullopt,
-                                       OptTensor dbeta_sink = std::nullopt) {
-  CHECK_IN(g); CHECK_IN(x);
+                                       bool relu, double keep_inv,
+                                       OptTensor dgamma_sink,
+                                       OptTensor dbeta_sink) {
+  const char* name = A16 ? "bn_relu_bwd16" : "bn_relu_bwd";
+  const bool b16 = bn_gate(name, A16, x, &g, &y);
   const long n = x.size(0);
   const int h = x.size(1);
   auto dx = torch::empty_like(x);
-  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, "bn_relu_bwd");
-  auto partials = torch::empty({2 * h}, x.options());
+  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, name);
+  auto partials =
+      torch::empty({2 * h}, x.options().dtype(torch::kFloat32));
   auto slab = bn_wide_slab(x);
-  launch_bn_bwd(g.data_ptr<float>(), x.data_ptr<float>(), y.data_ptr<float>(),
-                mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                gamma.data_ptr<float>(), partials.data_ptr<float>(),
-                dx.data_ptr<float>(), aff.pg, aff.pb, n, h, relu,
-                (float)keep_inv, bn_slab_ptr(slab), cur_stream(), aff.acc);
+  if (b16)
+    launch_bn_bwd16(g.data_ptr(), x.data_ptr(), y.data_ptr(),
+                    mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                    gamma.data_ptr<float>(), partials.data_ptr<float>(),
+                    dx.data_ptr(), aff.pg, aff.pb, n, h, relu, (float)keep_inv,
+                    bn_slab_ptr(slab), bn_mask_ptr(y, x), cur_stream(),
+                    aff.acc);
+  else
+    launch_bn_bwd(g.data_ptr<float>(), x.data_ptr<float>(),
+                  y.data_ptr<float>(), mean.data_ptr<float>(),
+                  invstd.data_ptr<float>(), gamma.data_ptr<float>(),
+                  partials.data_ptr<float>(), dx.data_ptr<float>(), aff.pg,
+                  aff.pb, n, h, relu, (float)keep_inv, bn_slab_ptr(slab),
+                  cur_stream(), aff.acc);
+  return {dx, aff.dgamma, aff.dbeta};
+}
+
+// The sync-BN pieces.  Partials are [2h+1]: per-channel sum / sum-of-squares
+// (backward: of gm and gm*xhat) plus the row count in the tail slot, so a
+// single all-reduce carries sums AND the global count with no host
+// round-trip (SURVEY.md §7 hard part 4).
+template <bool A16>
+std::vector<torch::Tensor> bn_finalize_apply(
+    torch::Tensor x, torch::Tensor partials, torch::Tensor gamma,
+    torch::Tensor beta, torch::Tensor running_mean, torch::Tensor running_var,
+    double momentum, double eps, bool training, bool relu, double dropout_p,
+    torch::Tensor seed) {
+  const char* name = A16 ? "bn_finalize_apply16" : "bn_finalize_apply";
+  const bool b16 = bn_gate(name, A16, x);
+  CHECK_IN(partials);
+  const int h = x.size(1);
+  bn_partials_check(name, partials, h);
+  auto fopt = x.options().dtype(torch::kFloat32);
+  auto y = torch::empty_like(x);
+  auto mean = torch::empty({h}, fopt);
+  auto invstd = torch::empty({h}, fopt);
+  const auto* sp = rng_seed_ptr(seed, dropout_p);
+  const float* pp = partials.data_ptr<float>();
+  torch::Tensor mask;
+  if (b16) {
+    mask = bn_new_mask(x, training, relu);
+    launch_bn_finalize_apply16(
+        x.data_ptr(), pp, pp + 2 * h, gamma.data_ptr<float>(),
+        beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+        running_var.data_ptr<float>(), mean.data_ptr<float>(),
+        invstd.data_ptr<float>(), y.data_ptr(), x.size(0), h, (float)momentum,
+        (float)eps, training, relu, (float)dropout_p, sp,
+        mask.numel() ? mask.data_ptr<unsigned char>() : nullptr, cur_stream());
+  } else {
+    launch_bn_finalize_apply(
+        x.data_ptr<float>(), pp, pp + 2 * h, gamma.data_ptr<float>(),
+        beta.data_ptr<float>(), running_mean.data_ptr<float>(),
+        running_var.data_ptr<float>(), mean.data_ptr<float>(),
+        invstd.data_ptr<float>(), y.data_ptr<float>(), x.size(0), h,
+        (float)momentum, (float)eps, training, relu, (float)dropout_p, sp,
+        cur_stream());
+  }
+  if (sp) launch_counter_bump((unsigned long long*)seed.data_ptr<long>(),
+                              cur_stream());
+  if (b16) return {y, mean, invstd, mask};
+  return {y, mean, invstd};
+}
+
+template <bool A16>
+torch::Tensor bn_bwd_partials(torch::Tensor g, torch::Tensor x,
+                              torch::Tensor y, torch::Tensor mean,
+                              torch::Tensor invstd, bool relu,
+                              double keep_inv) {
+  const bool b16 = bn_gate(A16 ? "bn_bwd_partials16" : "bn_bwd_partials", A16,
+                           x, &g, &y);
+  const long h = x.size(1);
+  auto partials =
+      torch::empty({2 * h + 1}, x.options().dtype(torch::kFloat32));
+  auto slab = bn_wide_slab(x);
+  if (b16)
+    launch_bn_bwd_partials_only16(
+        g.data_ptr(), x.data_ptr(), y.data_ptr(), mean.data_ptr<float>(),
+        invstd.data_ptr<float>(), x.size(0), h, relu,
+        partials.data_ptr<float>(), (float)keep_inv, bn_slab_ptr(slab),
+        bn_mask_ptr(y, x), cur_stream());
+  else
+    launch_bn_bwd_partials_only(
+        g.data_ptr<float>(), x.data_ptr<float>(), y.data_ptr<float>(),
+        mean.data_ptr<float>(), invstd.data_ptr<float>(), x.size(0), h, relu,
+        partials.data_ptr<float>(), (float)keep_inv, bn_slab_ptr(slab),
+        cur_stream());
+  partials.narrow(0, 2 * h, 1).fill_((float)x.size(0));
+  return partials;
+}
+
+template <bool A16>
+std::vector<torch::Tensor> bn_bwd_apply(
+    torch::Tensor g, torch::Tensor x, torch::Tensor y, torch::Tensor mean,
+    torch::Tensor invstd, torch::Tensor gamma, torch::Tensor partials_global,
+    torch::Tensor partials_local, bool relu, double keep_inv,
+    OptTensor dgamma_sink, OptTensor dbeta_sink) {
+  const char* name = A16 ? "bn_bwd_apply16" : "bn_bwd_apply";
+  const bool b16 = bn_gate(name, A16, x, &g, &y);
+  const int h = x.size(1);
+  bn_partials_check(name, partials_global, h);
+  auto dx = torch::empty_like(x);
+  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, name);
+  const float* pg = partials_global.data_ptr<float>();
+  if (b16)
+    launch_bn_bwd_apply_only16(
+        g.data_ptr(), x.data_ptr(), y.data_ptr(), mean.data_ptr<float>(),
+        invstd.data_ptr<float>(), gamma.data_ptr<float>(), pg, pg + 2 * h,
+        dx.data_ptr(), x.size(0), h, relu, (float)keep_inv, bn_mask_ptr(y, x),
+        cur_stream());
+  else
+    launch_bn_bwd_apply_only(
+        g.data_ptr<float>(), x.data_ptr<float>(), y.data_ptr<float>(),
+        mean.data_ptr<float>(), invstd.data_ptr<float>(),
+        gamma.data_ptr<float>(), pg, pg + 2 * h, dx.data_ptr<float>(),
+        x.size(0), h, relu, (float)keep_inv, cur_stream());
+  launch_bn_grad_affine(partials_local.data_ptr<float>(), aff.pg, aff.pb, h,
+                        cur_stream(), aff.acc);
   return {dx, aff.dgamma, aff.dbeta};
 }
 
@@ -654,185 +614,209 @@ void adam_step_ex(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                  cur_stream());
 }
 
-// y = x @ w^T + b (torch Linear layout: w [out,in]); bf16 variant rounds
-// operands to bf16 in the matrix cores (fp32 accumulate + output).
+// ---------------------------------------------------------------------------
+// Linear layers: y = x . w^T + b with x [m, k], w [n, k] (torch Linear
+// layout), g = dy [m, n]; dgrad dx = g . w, wgrad dw = g^T . x, db = column
+// sums of g.  Three families by the dtype of the activation streams:
+//   fp32-IO  linear_fwd* / linear_bwd* / linear_dgrad / linear_wgrad / gemm_*
+//   o16      linear_fwd_bf16_o16 / linear_dgrad16 / linear_wgrad16
+//   a16      linear_fwd_a16o16[_wt] / linear_dgrad16_o16 / linear_wgrad16_b16
+// ---------------------------------------------------------------------------
+
+enum LinOp { LIN_FWD, LIN_DGRAD, LIN_WGRAD };
+struct Mnk {
+  int m, n, k;
+};
+
+// The one shape and dtype gate of every linear binding.  The operands are
+// (x, w) forward, (g, w) dgrad and (g, x) wgrad, each of the dtype its family
+// requires; the launchers take int extents and trust that the operands agree,
+// so a mismatch stops here.  `bias`, where one is given (defined and not
+// empty), holds n fp32 elements.
+static Mnk linear_gate(const char* name, LinOp op, const torch::Tensor& a,
+                       at::ScalarType a_dtype, const torch::Tensor& b,
+                       at::ScalarType b_dtype,
+                       const torch::Tensor* bias = nullptr) {
+  const char* an = op == LIN_FWD ? "x" : "g";
+  const char* bn = op == LIN_WGRAD ? "x" : "w";
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2, name, ": ", an, " and ", bn,
+              " must be 2-D, got ", a.sizes(), " and ", b.sizes());
+  TORCH_CHECK(a.scalar_type() == a_dtype && b.scalar_type() == b_dtype, name,
+              ": ", an, " must be ", a_dtype, " and ", bn, " ", b_dtype,
+              ", got ", a.scalar_type(), " and ", b.scalar_type());
+  TORCH_CHECK(a.is_cuda() && a.device() == b.device(), name, ": ", an, " and ",
+              bn, " must be on the same GPU");
+  TORCH_CHECK(a.is_contiguous() && b.is_contiguous(), name, ": ", an, " and ",
+              bn, " must be contiguous");
+  int64_t m, n, k;
+  if (op == LIN_FWD) {  // x [m, k], w [n, k]
+    m = a.size(0), k = a.size(1), n = b.size(0);
+    TORCH_CHECK(b.size(1) == k, name, ": w is ", b.sizes(), " but x ",
+                a.sizes(), " has ", k, " columns");
+  } else if (op == LIN_DGRAD) {  // g [m, n], w [n, k]
+    m = a.size(0), n = b.size(0), k = b.size(1);
+    TORCH_CHECK(a.size(1) == n, name, ": g is ", a.sizes(), " but w ",
+                b.sizes(), " has ", n, " rows");
+  } else {  // g [m, n], x [m, k]
+    m = b.size(0), k = b.size(1), n = a.size(1);
+    TORCH_CHECK(a.size(0) == m, name, ": g is ", a.sizes(), " but x ",
+                b.sizes(), " has ", m, " rows");
+  }
+  TORCH_CHECK(m <= INT_MAX && n <= INT_MAX && k <= INT_MAX, name,
+              ": an extent of [", m, ", ", n, ", ", k, "] does not fit an int");
+  if (bias && bias->defined() && bias->numel() > 0)
+    TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->numel() == n &&
+                    bias->device() == a.device() && bias->is_contiguous(),
+                name, ": the bias must be ", n, " contiguous fp32 elements on "
+                "the operands' GPU, got ", bias->scalar_type(), " ",
+                bias->sizes());
+  return {(int)m, (int)n, (int)k};
+}
+
+static const float* bias_ptr(const torch::Tensor& b) {
+  return b.defined() && b.numel() > 0 ? b.data_ptr<float>() : nullptr;
+}
+
+// The fp32-IO launchers by compute precision: prec 0 = fp32, 1 = bf16 and
+// 2 = fp16 operands in the matrix cores (fp32 accumulate and output)
+struct GemmF32io {
+  decltype(&launch_gemm_f32_nt) nt;
+  decltype(&launch_gemm_f32_nn) nn;
+  decltype(&launch_gemm_f32_tn) tn;
+};
+static const GemmF32io& gemm_f32io(const char* name, int64_t prec) {
+  static const GemmF32io table[3] = {
+      {launch_gemm_f32_nt, launch_gemm_f32_nn, launch_gemm_f32_tn},
+      {launch_gemm_bf16_nt, launch_gemm_bf16_nn, launch_gemm_bf16_tn},
+      {launch_gemm_fp16_nt, launch_gemm_fp16_nn, launch_gemm_fp16_tn}};
+  TORCH_CHECK(prec >= 0 && prec <= 2, name,
+              ": prec must be 0 (fp32), 1 (bf16) or 2 (fp16), got ", prec);
+  return table[prec];
+}
+
+static torch::Tensor linear_fwd_f32io(const char* name, int64_t prec,
+                                      const torch::Tensor& x,
+                                      const torch::Tensor& w,
+                                      const torch::Tensor& b) {
+  const auto& gemm = gemm_f32io(name, prec);
+  const auto [m, n, k] = linear_gate(name, LIN_FWD, x, torch::kFloat32, w,
+                                     torch::kFloat32, &b);
+  auto y = torch::empty({m, n}, x.options());
+  if (m == 0) return y;  // no rows: nothing to launch
+  gemm.nt(x.data_ptr<float>(), w.data_ptr<float>(), bias_ptr(b),
+          y.data_ptr<float>(), m, n, k, false, cur_stream());
+  return y;
+}
+
+static torch::Tensor linear_dgrad_f32io(const char* name, int64_t prec,
+                                        const torch::Tensor& g,
+                                        const torch::Tensor& w) {
+  const auto& gemm = gemm_f32io(name, prec);
+  const auto [m, n, k] = linear_gate(name, LIN_DGRAD, g, torch::kFloat32, w,
+                                     torch::kFloat32);
+  auto dx = torch::empty({m, k}, g.options());
+  if (m == 0) return dx;  // no rows: nothing to launch
+  gemm.nn(g.data_ptr<float>(), w.data_ptr<float>(), nullptr,
+          dx.data_ptr<float>(), m, n, k, false, cur_stream());
+  return dx;
+}
+
+// -> {dw [n, k], db [n] or [0]}
+static std::vector<torch::Tensor> linear_wgrad_f32io(const char* name,
+                                                     int64_t prec,
+                                                     const torch::Tensor& g,
+                                                     const torch::Tensor& x,
+                                                     bool has_bias) {
+  const auto& gemm = gemm_f32io(name, prec);
+  const auto [m, n, k] = linear_gate(name, LIN_WGRAD, g, torch::kFloat32, x,
+                                     torch::kFloat32);
+  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
+    return {torch::zeros({n, k}, x.options()),
+            torch::zeros({has_bias ? n : 0}, g.options())};
+  auto dw = torch::empty({n, k}, x.options());
+  auto db = torch::empty({has_bias ? n : 0}, g.options());
+  gemm.tn(g.data_ptr<float>(), x.data_ptr<float>(), dw.data_ptr<float>(),
+          has_bias ? db.data_ptr<float>() : nullptr, m, n, k, cur_stream());
+  return {dw, db};
+}
+
+// The raw GEMMs (tests / future fused paths) are the linear ops without a
+// bias: gemm_nt(a, b) = a . b^T, gemm_nn(a, b) = a . b, gemm_tn(a, b) =
+// a^T . b (zeros for an empty contraction)
+static torch::Tensor gemm_raw_f32io(const char* name, LinOp op, int64_t prec,
+                                    const torch::Tensor& a,
+                                    const torch::Tensor& b) {
+  if (op == LIN_FWD) return linear_fwd_f32io(name, prec, a, b, {});
+  if (op == LIN_DGRAD) return linear_dgrad_f32io(name, prec, a, b);
+  return linear_wgrad_f32io(name, prec, a, b, false)[0];
+}
+
+// dgrad, then wgrad: -> {dx, dw, db}.  x against w and g against x are
+// checked here and g against w by the dgrad, so all three agree before the
+// first launch.
+static std::vector<torch::Tensor> linear_bwd_f32io(const char* name,
+                                                   int64_t prec,
+                                                   const torch::Tensor& g,
+                                                   const torch::Tensor& x,
+                                                   const torch::Tensor& w,
+                                                   bool has_bias) {
+  linear_gate(name, LIN_FWD, x, torch::kFloat32, w, torch::kFloat32);
+  linear_gate(name, LIN_WGRAD, g, torch::kFloat32, x, torch::kFloat32);
+  auto dx = linear_dgrad_f32io(name, prec, g, w);
+  auto dwb = linear_wgrad_f32io(name, prec, g, x, has_bias);
+  return {dx, dwb[0], dwb[1]};
+}
+
+using TensorList = std::vector<torch::Tensor>;
+torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b) {
+  return linear_fwd_f32io("linear_fwd", 0, x, w, b);
+}
 torch::Tensor linear_fwd_bf16(torch::Tensor x, torch::Tensor w,
                               torch::Tensor b) {
-  CHECK_IN(x); CHECK_IN(w);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = w.size(0);
-  auto y = torch::empty({m, n}, x.options());
-  if (m == 0) return y;  // no rows: nothing to launch
-  const float* bias = nullptr;
-  if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
-  launch_gemm_bf16_nt(x.data_ptr<float>(), w.data_ptr<float>(), bias,
-                      y.data_ptr<float>(), m, n, k, false, cur_stream());
-  return y;
+  return linear_fwd_f32io("linear_fwd_bf16", 1, x, w, b);
 }
-
-std::vector<torch::Tensor> linear_bwd_bf16(torch::Tensor g, torch::Tensor x,
-                                           torch::Tensor w, bool has_bias) {
-  CHECK_IN(g); CHECK_IN(x); CHECK_IN(w);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = w.size(0);
-  auto dx = torch::empty({m, k}, x.options());
-  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
-    return {dx, torch::zeros({n, k}, w.options()),
-            torch::zeros({has_bias ? n : 0}, g.options())};
-  auto dw = torch::empty({n, k}, w.options());
-  torch::Tensor db = torch::empty({0}, g.options());
-  float* db_ptr = nullptr;
-  if (has_bias) {
-    db = torch::empty({n}, g.options());
-    db_ptr = db.data_ptr<float>();
-  }
-  launch_gemm_bf16_nn(g.data_ptr<float>(), w.data_ptr<float>(), nullptr,
-                      dx.data_ptr<float>(), m, n, k, false, cur_stream());
-  launch_gemm_bf16_tn(g.data_ptr<float>(), x.data_ptr<float>(),
-                      dw.data_ptr<float>(), db_ptr, m, n, k, cur_stream());
-  return {dx, dw, db};
-}
-
-torch::Tensor gemm_nt_bf16(torch::Tensor a, torch::Tensor b) {
-  CHECK_IN(a); CHECK_IN(b);
-  auto c = torch::empty({a.size(0), b.size(0)}, a.options());
-  if (a.size(0) == 0) return c;  // no rows: nothing to launch
-  launch_gemm_bf16_nt(a.data_ptr<float>(), b.data_ptr<float>(), nullptr,
-                      c.data_ptr<float>(), a.size(0), b.size(0), a.size(1),
-                      false, cur_stream());
-  return c;
-}
-torch::Tensor gemm_nn_bf16(torch::Tensor a, torch::Tensor b) {
-  CHECK_IN(a); CHECK_IN(b);
-  auto c = torch::empty({a.size(0), b.size(1)}, a.options());
-  if (a.size(0) == 0) return c;  // no rows: nothing to launch
-  launch_gemm_bf16_nn(a.data_ptr<float>(), b.data_ptr<float>(), nullptr,
-                      c.data_ptr<float>(), a.size(0), a.size(1), b.size(1),
-                      false, cur_stream());
-  return c;
-}
-torch::Tensor gemm_tn_bf16(torch::Tensor a, torch::Tensor b) {
-  CHECK_IN(a); CHECK_IN(b);
-  if (a.size(0) == 0)  // empty contraction: zeros, nothing to launch
-    return torch::zeros({a.size(1), b.size(1)}, a.options());
-  auto c = torch::empty({a.size(1), b.size(1)}, a.options());
-  launch_gemm_bf16_tn(a.data_ptr<float>(), b.data_ptr<float>(),
-                      c.data_ptr<float>(), nullptr, a.size(0), a.size(1),
-                      b.size(1), cur_stream());
-  return c;
-}
-
 torch::Tensor linear_fwd_fp16(torch::Tensor x, torch::Tensor w,
                               torch::Tensor b) {
-  CHECK_IN(x); CHECK_IN(w);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = w.size(0);
-  auto y = torch::empty({m, n}, x.options());
-  if (m == 0) return y;  // no rows: nothing to launch
-  const float* bias = nullptr;
-  if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
-  launch_gemm_fp16_nt(x.data_ptr<float>(), w.data_ptr<float>(), bias,
-                      y.data_ptr<float>(), m, n, k, false, cur_stream());
-  return y;
+  return linear_fwd_f32io("linear_fwd_fp16", 2, x, w, b);
 }
-
-std::vector<torch::Tensor> linear_bwd_fp16(torch::Tensor g, torch::Tensor x,
-                                           torch::Tensor w, bool has_bias) {
-  CHECK_IN(g); CHECK_IN(x); CHECK_IN(w);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = w.size(0);
-  auto dx = torch::empty({m, k}, x.options());
-  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
-    return {dx, torch::zeros({n, k}, w.options()),
-            torch::zeros({has_bias ? n : 0}, g.options())};
-  auto dw = torch::empty({n, k}, w.options());
-  torch::Tensor db = torch::empty({0}, g.options());
-  float* db_ptr = nullptr;
-  if (has_bias) {
-    db = torch::empty({n}, g.options());
-    db_ptr = db.data_ptr<float>();
-  }
-  launch_gemm_fp16_nn(g.data_ptr<float>(), w.data_ptr<float>(), nullptr,
-                      dx.data_ptr<float>(), m, n, k, false, cur_stream());
-  launch_gemm_fp16_tn(g.data_ptr<float>(), x.data_ptr<float>(),
-                      dw.data_ptr<float>(), db_ptr, m, n, k, cur_stream());
-  return {dx, dw, db};
+TensorList linear_bwd(torch::Tensor g, torch::Tensor x, torch::Tensor w,
+                   bool has_bias) {
+  return linear_bwd_f32io("linear_bwd", 0, g, x, w, has_bias);
 }
-
-torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor b) {
-  CHECK_IN(x); CHECK_IN(w);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = w.size(0);
-  TORCH_CHECK(w.size(1) == k, "weight shape mismatch");
-  auto y = torch::empty({m, n}, x.options());
-  if (m == 0) return y;  // no rows: nothing to launch
-  const float* bias = nullptr;
-  if (b.defined() && b.numel() > 0) {
-    CHECK_IN(b);
-    bias = b.data_ptr<float>();
-  }
-  launch_gemm_f32_nt(x.data_ptr<float>(), w.data_ptr<float>(), bias,
-                     y.data_ptr<float>(), m, n, k, false, cur_stream());
-  return y;
+TensorList linear_bwd_bf16(torch::Tensor g, torch::Tensor x, torch::Tensor w,
+                        bool has_bias) {
+  return linear_bwd_f32io("linear_bwd_bf16", 1, g, x, w, has_bias);
 }
-
-std::vector<torch::Tensor> linear_bwd(torch::Tensor g, torch::Tensor x,
-                                      torch::Tensor w, bool has_bias) {
-  CHECK_IN(g); CHECK_IN(x); CHECK_IN(w);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = w.size(0);
-  auto dx = torch::empty({m, k}, x.options());
-  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
-    return {dx, torch::zeros({n, k}, w.options()),
-            torch::zeros({has_bias ? n : 0}, g.options())};
-  auto dw = torch::empty({n, k}, w.options());
-  torch::Tensor db = torch::empty({0}, g.options());
-  float* db_ptr = nullptr;
-  if (has_bias) {
-    db = torch::empty({n}, g.options());
-    db_ptr = db.data_ptr<float>();
-  }
-  launch_gemm_f32_nn(g.data_ptr<float>(), w.data_ptr<float>(), nullptr,
-                     dx.data_ptr<float>(), m, n, k, false, cur_stream());
-  launch_gemm_f32_tn(g.data_ptr<float>(), x.data_ptr<float>(),
-                     dw.data_ptr<float>(), db_ptr, m, n, k, cur_stream());
-  return {dx, dw, db};
+TensorList linear_bwd_fp16(torch::Tensor g, torch::Tensor x, torch::Tensor w,
+                        bool has_bias) {
+  return linear_bwd_f32io("linear_bwd_fp16", 2, g, x, w, has_bias);
 }
-
-// raw GEMM entry points (tests / future fused paths)
+// split backward entry points so python can overlap dgrad (current stream)
+// with wgrad+bias-grad (side stream)
+torch::Tensor linear_dgrad(torch::Tensor g, torch::Tensor w, int64_t prec) {
+  return linear_dgrad_f32io("linear_dgrad", prec, g, w);
+}
+TensorList linear_wgrad(torch::Tensor g, torch::Tensor x, bool has_bias,
+                     int64_t prec) {
+  return linear_wgrad_f32io("linear_wgrad", prec, g, x, has_bias);
+}
 torch::Tensor gemm_nt(torch::Tensor a, torch::Tensor b) {
-  CHECK_IN(a); CHECK_IN(b);
-  auto c = torch::empty({a.size(0), b.size(0)}, a.options());
-  if (a.size(0) == 0) return c;  // no rows: nothing to launch
-  launch_gemm_f32_nt(a.data_ptr<float>(), b.data_ptr<float>(), nullptr,
-                     c.data_ptr<float>(), a.size(0), b.size(0), a.size(1),
-                     false, cur_stream());
-  return c;
+  return gemm_raw_f32io("gemm_nt", LIN_FWD, 0, a, b);
 }
 torch::Tensor gemm_nn(torch::Tensor a, torch::Tensor b) {
-  CHECK_IN(a); CHECK_IN(b);
-  auto c = torch::empty({a.size(0), b.size(1)}, a.options());
-  if (a.size(0) == 0) return c;  // no rows: nothing to launch
-  launch_gemm_f32_nn(a.data_ptr<float>(), b.data_ptr<float>(), nullptr,
-                     c.data_ptr<float>(), a.size(0), a.size(1), b.size(1),
-                     false, cur_stream());
-  return c;
+  return gemm_raw_f32io("gemm_nn", LIN_DGRAD, 0, a, b);
 }
 torch::Tensor gemm_tn(torch::Tensor a, torch::Tensor b) {
-  CHECK_IN(a); CHECK_IN(b);
-  if (a.size(0) == 0)  // empty contraction: zeros, nothing to launch
-    return torch::zeros({a.size(1), b.size(1)}, a.options());
-  auto c = torch::empty({a.size(1), b.size(1)}, a.options());
-  launch_gemm_f32_tn(a.data_ptr<float>(), b.data_ptr<float>(),
-                     c.data_ptr<float>(), nullptr, a.size(0), a.size(1),
-                     b.size(1), cur_stream());
-  return c;
+  return gemm_raw_f32io("gemm_tn", LIN_WGRAD, 0, a, b);
+}
+torch::Tensor gemm_nt_bf16(torch::Tensor a, torch::Tensor b) {
+  return gemm_raw_f32io("gemm_nt_bf16", LIN_FWD, 1, a, b);
+}
+torch::Tensor gemm_nn_bf16(torch::Tensor a, torch::Tensor b) {
+  return gemm_raw_f32io("gemm_nn_bf16", LIN_DGRAD, 1, a, b);
+}
+torch::Tensor gemm_tn_bf16(torch::Tensor a, torch::Tensor b) {
+  return gemm_raw_f32io("gemm_tn_bf16", LIN_WGRAD, 1, a, b);
 }
 
 // dtable[r] = sum over g rows whose table index is r; order/ptr group the
@@ -1011,23 +995,148 @@ torch::Tensor embed_dgrad_fold(torch::Tensor dqkvs, torch::Tensor idx1,
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// Fused edge attention over qkvs [N, 4h] (fp32 or bf16), the two P tables
+// (fp32, or bf16 with bf16 qkvs), edge_attr [E, >=2] and the CSR arrays.
+// ---------------------------------------------------------------------------
+
+struct AttnShape {
+  int n, h;
+  long ne;
+  bool b16, p16;  // bf16 qkvs / bf16 P tables
+};
+
+// The checks every fused-attention binding shares (the forward half)
+static AttnShape attn_gate(const char* name, const torch::Tensor& qkvs,
+                           const torch::Tensor& pifc,
+                           const torch::Tensor& prpc, const torch::Tensor& ea,
+                           const torch::Tensor& row_ptr,
+                           const torch::Tensor& csr_src, int64_t heads) {
+  for (const auto* t : {&qkvs, &pifc, &prpc, &ea, &row_ptr, &csr_src})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->device() == qkvs.device(),
+                name, ": every operand must be contiguous and on one GPU");
+  TORCH_CHECK(qkvs.dim() == 2 && qkvs.size(1) % 4 == 0 &&
+                  qkvs.size(0) <= INT_MAX,
+              name, ": qkvs must be [N, 4h]");
+  AttnShape s;
+  s.n = (int)qkvs.size(0);
+  s.h = (int)(qkvs.size(1) / 4);
+  s.ne = ea.size(0);
+  s.b16 = qkvs.scalar_type() == torch::kBFloat16;
+  s.p16 = pifc.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(s.h <= 512, name, ": H must be <= 512");
+  TORCH_CHECK(heads >= 1 && heads <= s.h && s.h % heads == 0, name,
+              ": heads must divide H (H=", s.h, ", heads=", heads, ")");
+  TORCH_CHECK(s.b16 || qkvs.scalar_type() == torch::kFloat32, name,
+              ": qkvs must be fp32 or bf16");
+  TORCH_CHECK(!s.p16 || s.b16, name, ": bf16 P tables require bf16 qkvs");
+  TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(), name,
+              ": P tables must share a dtype");
+  TORCH_CHECK(s.p16 || pifc.scalar_type() == torch::kFloat32, name,
+              ": P tables must be fp32 or bf16");
+  TORCH_CHECK(pifc.dim() == 2 && prpc.dim() == 2 && pifc.size(1) == s.h &&
+                  prpc.size(1) == s.h,
+              name, ": P tables must have width h");
+  TORCH_CHECK(ea.dim() == 2 && ea.size(1) >= 2 &&
+                  ea.scalar_type() == torch::kLong,
+              name, ": edge_attr must be int64 [E, >=2]");
+  TORCH_CHECK(row_ptr.scalar_type() == torch::kInt32 &&
+                  csr_src.scalar_type() == torch::kInt32 &&
+                  row_ptr.numel() == (int64_t)s.n + 1 &&
+                  csr_src.numel() == s.ne,
+              name, ": CSR arrays (int32) do not match qkvs/edge_attr");
+  return s;
+}
+
+// The backward, shared by edge_attn_fused_bwd, edge_attn_bn_bwd16 and
+// edge_attn_pool_bwd16.  Constructing it checks the operands (the forward's
+// checks, alpha of the forward, the CSC arrays, and g [n, h] where there is
+// one: the pool mode forms it itself), so a binding can launch what must
+// precede the attention kernels in between; run() allocates {dqkvs, de} and
+// launches.  The softmax backward is single-pass: no [E, h] dek/dev scratch,
+// the col kernel regenerates the rank-1 per-edge grads from the per-edge
+// scalars (dal = logit grad, alpha) and row gathers of q/g.
+struct AttnBwd {
+  const torch::Tensor *g, &qkvs, &pifc, &prpc, &ea, &alpha, &row_ptr, &csr_src,
+      &col_ptr, &csc_dst, &csc_eid;
+  const int64_t heads;
+  const AttnShape s;
+
+  AttnBwd(const char* name, const torch::Tensor* g, const torch::Tensor& qkvs,
+          const torch::Tensor& pifc, const torch::Tensor& prpc,
+          const torch::Tensor& ea, const torch::Tensor& alpha,
+          const torch::Tensor& row_ptr, const torch::Tensor& csr_src,
+          const torch::Tensor& col_ptr, const torch::Tensor& csc_dst,
+          const torch::Tensor& csc_eid, int64_t heads)
+      : g(g), qkvs(qkvs), pifc(pifc), prpc(prpc), ea(ea), alpha(alpha),
+        row_ptr(row_ptr), csr_src(csr_src), col_ptr(col_ptr), csc_dst(csc_dst),
+        csc_eid(csc_eid), heads(heads),
+        s(attn_gate(name, qkvs, pifc, prpc, ea, row_ptr, csr_src, heads)) {
+    for (const auto* t : {&alpha, &col_ptr, &csc_dst, &csc_eid})
+      TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                      t->device() == qkvs.device(),
+                  name, ": every operand must be contiguous and on one GPU");
+    TORCH_CHECK(alpha.scalar_type() == torch::kFloat32 &&
+                    alpha.numel() == s.ne * heads,
+                name,
+                ": alpha must be the fp32 [E, heads] tensor of the forward");
+    TORCH_CHECK(col_ptr.scalar_type() == torch::kInt32 &&
+                    csc_dst.scalar_type() == torch::kInt32 &&
+                    csc_eid.scalar_type() == torch::kInt32 &&
+                    col_ptr.numel() == (int64_t)s.n + 1 &&
+                    csc_dst.numel() == s.ne && csc_eid.numel() == s.ne,
+                name, ": CSC arrays (int32) do not match qkvs/edge_attr");
+    TORCH_CHECK(g || s.b16, name, " takes bf16 qkvs");
+    if (g)
+      TORCH_CHECK(g->is_cuda() && g->is_contiguous() && g->dim() == 2 &&
+                      g->size(0) == s.n && g->size(1) == s.h &&
+                      (g->scalar_type() == torch::kFloat32 ||
+                       (s.b16 && g->scalar_type() == torch::kBFloat16)),
+                  name, ": g must be [n, h], fp32 (or bf16 with bf16 qkvs)");
+  }
+
+  // bn / pool (bf16 qkvs only) as in launch_edge_attn_fused_bwd16
+  std::vector<torch::Tensor> run(const AttnBnBwd* bn = nullptr,
+                                 const AttnPoolBwd* pool = nullptr) const {
+    auto fopt = qkvs.options().dtype(torch::kFloat32);
+    auto dqkvs = torch::empty_like(qkvs);
+    // edge scratch matches qkvs dtype
+    auto de = torch::empty({s.ne, s.h}, s.b16 ? qkvs.options() : fopt);
+    auto dal = torch::empty({s.ne * heads}, fopt);  // [E, heads] row-major
+    if (s.b16) {
+      const int g16 = g && g->scalar_type() == torch::kBFloat16 ? 1 : 0;
+      launch_edge_attn_fused_bwd16(
+          g ? g->data_ptr() : nullptr, g16, qkvs.data_ptr(), pifc.data_ptr(),
+          prpc.data_ptr(), s.p16 ? 1 : 0, ea.data_ptr<long>(),
+          (int)ea.size(1), alpha.data_ptr<float>(), row_ptr.data_ptr<int>(),
+          csr_src.data_ptr<int>(), col_ptr.data_ptr<int>(),
+          csc_dst.data_ptr<int>(), csc_eid.data_ptr<int>(), dqkvs.data_ptr(),
+          de.data_ptr(), dal.data_ptr<float>(), s.n, s.h, s.ne, (int)heads,
+          cur_stream(), bn, pool);
+    } else {
+      TORCH_CHECK(!bn && !pool, "the fused BN / pool backward needs bf16 qkvs");
+      launch_edge_attn_fused_bwd(
+          g->data_ptr<float>(), qkvs.data_ptr<float>(),
+          pifc.data_ptr<float>(), prpc.data_ptr<float>(), ea.data_ptr<long>(),
+          (int)ea.size(1), alpha.data_ptr<float>(), row_ptr.data_ptr<int>(),
+          csr_src.data_ptr<int>(), col_ptr.data_ptr<int>(),
+          csc_dst.data_ptr<int>(), csc_eid.data_ptr<int>(),
+          dqkvs.data_ptr<float>(), de.data_ptr<float>(),
+          dal.data_ptr<float>(), s.n, s.h, s.ne, (int)heads, cur_stream());
+    }
+    return {dqkvs, de};
+  }
+};
+
 std::vector<torch::Tensor> edge_attn_fused_fwd(
     torch::Tensor qkvs, torch::Tensor pifc, torch::Tensor prpc,
     torch::Tensor ea, torch::Tensor row_ptr, torch::Tensor csr_src,
     bool out16, int64_t heads = 1) {
-  CHECK_IN(qkvs); CHECK_IN(pifc); CHECK_IN(prpc); CHECK_IN(ea);
-  const int n = qkvs.size(0);
-  const int h = qkvs.size(1) / 4;
-  TORCH_CHECK(h <= 512, "H must be <= 512");
-  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
-              "heads must divide H (H=", h, ", heads=", heads, ")");
+  const auto [n, h, ne, b16, p16] = attn_gate(
+      "edge_attn_fused_fwd", qkvs, pifc, prpc, ea, row_ptr, csr_src, heads);
+  TORCH_CHECK(!out16 || b16, "edge_attn_fused_fwd: out16 requires bf16 qkvs");
   auto fopt = qkvs.options().dtype(torch::kFloat32);
-  const bool b16 = qkvs.scalar_type() == torch::kBFloat16;
-  const bool p16 = pifc.scalar_type() == torch::kBFloat16;
-  TORCH_CHECK(!out16 || b16, "out16 requires bf16 qkvs");
-  TORCH_CHECK(!p16 || b16, "bf16 P tables require bf16 qkvs");
-  TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(),
-              "P tables must share a dtype");
   auto out = torch::empty({n, h}, out16 ? qkvs.options() : fopt);
   // per-(edge, head) attention weights: [E] single-head, [E, heads] otherwise
   auto alpha = heads == 1 ? torch::empty({ea.size(0)}, fopt)
@@ -1058,35 +1167,10 @@ torch::Tensor edge_attn_fused_infer(
     torch::Tensor ea, torch::Tensor row_ptr, torch::Tensor csr_src,
     torch::Tensor bn_scale, torch::Tensor bn_shift, bool relu, bool out16,
     int64_t heads = 1) {
-  CHECK_IN(qkvs); CHECK_IN(pifc); CHECK_IN(prpc); CHECK_IN(ea);
-  CHECK_IN(row_ptr); CHECK_IN(csr_src);
-  TORCH_CHECK(qkvs.dim() == 2 && qkvs.size(1) % 4 == 0,
-              "qkvs must be [N, 4h]");
-  const int n = qkvs.size(0);
-  const int h = qkvs.size(1) / 4;
-  TORCH_CHECK(qkvs.size(1) == 4 * (int64_t)h, "qkvs must be [N, 4h]");
-  TORCH_CHECK(h <= 512, "H must be <= 512");
-  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
-              "heads must divide H (H=", h, ", heads=", heads, ")");
-  const bool b16 = qkvs.scalar_type() == torch::kBFloat16;
-  const bool p16 = pifc.scalar_type() == torch::kBFloat16;
-  TORCH_CHECK(b16 || qkvs.scalar_type() == torch::kFloat32,
-              "qkvs must be fp32 or bf16");
-  TORCH_CHECK(!out16 || b16, "out16 requires bf16 qkvs");
-  TORCH_CHECK(!p16 || b16, "bf16 P tables require bf16 qkvs");
-  TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(),
-              "P tables must share a dtype");
-  TORCH_CHECK(p16 || pifc.scalar_type() == torch::kFloat32,
-              "P tables must be fp32 or bf16");
-  TORCH_CHECK(pifc.dim() == 2 && prpc.dim() == 2 && pifc.size(1) == h &&
-                  prpc.size(1) == h,
-              "P tables must have width h");
-  TORCH_CHECK(ea.dim() == 2 && ea.size(1) >= 2 &&
-                  ea.scalar_type() == torch::kLong,
-              "edge_attr must be int64 [E, >=2]");
-  TORCH_CHECK(row_ptr.numel() == (int64_t)n + 1 &&
-                  csr_src.numel() == ea.size(0),
-              "CSR arrays do not match qkvs/edge_attr");
+  const auto [n, h, ne, b16, p16] = attn_gate(
+      "edge_attn_fused_infer", qkvs, pifc, prpc, ea, row_ptr, csr_src, heads);
+  TORCH_CHECK(!out16 || b16,
+              "edge_attn_fused_infer: out16 requires bf16 qkvs");
   TORCH_CHECK(bn_scale.numel() == bn_shift.numel() &&
                   (bn_scale.numel() == 0 || bn_scale.numel() == h),
               "bn_scale/bn_shift must both be empty or both have h elements");
@@ -1127,46 +1211,9 @@ std::vector<torch::Tensor> edge_attn_fused_bwd(
     torch::Tensor prpc, torch::Tensor ea, torch::Tensor alpha,
     torch::Tensor row_ptr, torch::Tensor csr_src, torch::Tensor col_ptr,
     torch::Tensor csc_dst, torch::Tensor csc_eid, int64_t heads = 1) {
-  CHECK_IN(g); CHECK_IN(qkvs); CHECK_IN(alpha);
-  const int n = qkvs.size(0);
-  const int h = qkvs.size(1) / 4;
-  const long ne = ea.size(0);
-  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
-              "heads must divide H (H=", h, ", heads=", heads, ")");
-  TORCH_CHECK(alpha.scalar_type() == torch::kFloat32 &&
-                  alpha.numel() == ne * heads,
-              "alpha must be the fp32 [E, heads] tensor of the forward");
-  auto fopt = qkvs.options().dtype(torch::kFloat32);
-  auto dqkvs = torch::empty_like(qkvs);
-  const bool b16 = qkvs.scalar_type() == torch::kBFloat16;
-  auto eopt = b16 ? qkvs.options() : fopt;  // edge scratch matches qkvs dtype
-  // single-pass softmax backward: the [E,h] dek/dev scratch is gone — the
-  // col kernel regenerates the rank-1 per-edge grads from the per-edge
-  // scalars (dal = logit grad, alpha) and row gathers of q/g
-  auto de = torch::empty({ne, h}, eopt);
-  auto dal = torch::empty({ne * heads}, fopt);  // [E, heads] row-major
-  if (b16) {
-    const int g16 = g.scalar_type() == torch::kBFloat16 ? 1 : 0;
-    const int p16 = pifc.scalar_type() == torch::kBFloat16 ? 1 : 0;
-    launch_edge_attn_fused_bwd16(
-        g.data_ptr(), g16, qkvs.data_ptr(),
-        pifc.data_ptr(), prpc.data_ptr(), p16, ea.data_ptr<long>(),
-        (int)ea.size(1), alpha.data_ptr<float>(), row_ptr.data_ptr<int>(),
-        csr_src.data_ptr<int>(), col_ptr.data_ptr<int>(),
-        csc_dst.data_ptr<int>(), csc_eid.data_ptr<int>(), dqkvs.data_ptr(),
-        de.data_ptr(), dal.data_ptr<float>(), n, h, ne, (int)heads,
-        cur_stream());
-  } else {
-    launch_edge_attn_fused_bwd(
-        g.data_ptr<float>(), qkvs.data_ptr<float>(), pifc.data_ptr<float>(),
-        prpc.data_ptr<float>(), ea.data_ptr<long>(), (int)ea.size(1),
-        alpha.data_ptr<float>(), row_ptr.data_ptr<int>(),
-        csr_src.data_ptr<int>(), col_ptr.data_ptr<int>(),
-        csc_dst.data_ptr<int>(), csc_eid.data_ptr<int>(),
-        dqkvs.data_ptr<float>(), de.data_ptr<float>(), dal.data_ptr<float>(),
-        n, h, ne, (int)heads, cur_stream());
-  }
-  return {dqkvs, de};
+  return AttnBwd("edge_attn_fused_bwd", &g, qkvs, pifc, prpc, ea, alpha,
+                 row_ptr, csr_src, col_ptr, csc_dst, csc_eid, heads)
+      .run();
 }
 
 // dtable[v] += sum of g[r, col_off:col_off+h] over rows r with idx[r]==v.
@@ -1218,128 +1265,6 @@ torch::Tensor bn_stats(torch::Tensor x) {
   return partials;
 }
 
-std::vector<torch::Tensor> bn_finalize_apply(
-    torch::Tensor x, torch::Tensor partials,
-    torch::Tensor gamma, torch::Tensor beta, torch::Tensor running_mean,
-    torch::Tensor running_var, double momentum, double eps, bool training,
-    bool relu, double dropout_p = 0.0, torch::Tensor seed = {}) {
-  CHECK_IN(x); CHECK_IN(partials);
-  const int h = x.size(1);
-  TORCH_CHECK(partials.numel() == 2 * h + 1,
-              "bn_finalize_apply expects [2h+1] partials with the global "
-              "count in the tail slot");
-  auto y = torch::empty_like(x);
-  auto mean = torch::empty({h}, x.options());
-  auto invstd = torch::empty({h}, x.options());
-  const auto* sp = rng_seed_ptr(seed, dropout_p);
-  launch_bn_finalize_apply(
-      x.data_ptr<float>(), partials.data_ptr<float>(),
-      partials.data_ptr<float>() + 2 * h,
-      gamma.data_ptr<float>(), beta.data_ptr<float>(),
-      running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
-      mean.data_ptr<float>(), invstd.data_ptr<float>(), y.data_ptr<float>(),
-      x.size(0), h, (float)momentum, (float)eps, training, relu,
-      (float)dropout_p, sp, cur_stream());
-  if (sp) launch_counter_bump((unsigned long long*)seed.data_ptr<long>(),
-                              cur_stream());
-  return {y, mean, invstd};
-}
-
-torch::Tensor bn_bwd_partials(torch::Tensor g, torch::Tensor x,
-                              torch::Tensor y, torch::Tensor mean,
-                              torch::Tensor invstd, bool relu,
-                              double keep_inv = 1.0) {
-  CHECK_IN(g); CHECK_IN(x);
-  const long h = x.size(1);
-  auto partials = torch::empty({2 * h + 1}, x.options());
-  auto slab = bn_wide_slab(x);
-  launch_bn_bwd_partials_only(g.data_ptr<float>(), x.data_ptr<float>(),
-                              y.data_ptr<float>(), mean.data_ptr<float>(),
-                              invstd.data_ptr<float>(), x.size(0), h,
-                              relu, partials.data_ptr<float>(),
-                              (float)keep_inv, bn_slab_ptr(slab),
-                              cur_stream());
-  partials.narrow(0, 2 * h, 1).fill_((float)x.size(0));
-  return partials;
-}
-
-std::vector<torch::Tensor> bn_bwd_apply(torch::Tensor g, torch::Tensor x,
-                                        torch::Tensor y, torch::Tensor mean,
-                                        torch::Tensor invstd,
-                                        torch::Tensor gamma,
-                                        torch::Tensor partials_global,
-                                        torch::Tensor partials_local,
-                                        bool relu, double keep_inv = 1.0,
-                                        OptTensor dgamma_sink = std::nullopt,
-                                        OptTensor dbeta_sink = std::nullopt) {
-  CHECK_IN(g); CHECK_IN(x);
-  const int h = x.size(1);
-  TORCH_CHECK(partials_global.numel() == 2 * h + 1,
-              "bn_bwd_apply expects [2h+1] partials with the global count "
-              "in the tail slot");
-  auto dx = torch::empty_like(x);
-  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, "bn_bwd_apply");
-  launch_bn_bwd_apply_only(g.data_ptr<float>(), x.data_ptr<float>(),
-                           y.data_ptr<float>(), mean.data_ptr<float>(),
-                           invstd.data_ptr<float>(), gamma.data_ptr<float>(),
-                           partials_global.data_ptr<float>(),
-                           partials_global.data_ptr<float>() + 2 * h,
-                           dx.data_ptr<float>(), x.size(0), h, relu,
-                           (float)keep_inv, cur_stream());
-  launch_bn_grad_affine(partials_local.data_ptr<float>(), aff.pg, aff.pb, h,
-                        cur_stream(), aff.acc);
-  return {dx, aff.dgamma, aff.dbeta};
-}
-
-// split backward entry points so python can overlap dgrad (current stream)
-// with wgrad+bias-grad (side stream): prec 0=f32, 1=bf16, 2=fp16
-torch::Tensor linear_dgrad(torch::Tensor g, torch::Tensor w, int64_t prec) {
-  CHECK_IN(g); CHECK_IN(w);
-  const int m = g.size(0);
-  const int n = w.size(0);
-  const int k = w.size(1);
-  auto dx = torch::empty({m, k}, g.options());
-  if (m == 0) return dx;  // no rows: nothing to launch
-  if (prec == 1)
-    launch_gemm_bf16_nn(g.data_ptr<float>(), w.data_ptr<float>(), nullptr,
-                        dx.data_ptr<float>(), m, n, k, false, cur_stream());
-  else if (prec == 2)
-    launch_gemm_fp16_nn(g.data_ptr<float>(), w.data_ptr<float>(), nullptr,
-                        dx.data_ptr<float>(), m, n, k, false, cur_stream());
-  else
-    launch_gemm_f32_nn(g.data_ptr<float>(), w.data_ptr<float>(), nullptr,
-                       dx.data_ptr<float>(), m, n, k, false, cur_stream());
-  return dx;
-}
-
-std::vector<torch::Tensor> linear_wgrad(torch::Tensor g, torch::Tensor x,
-                                        bool has_bias, int64_t prec) {
-  CHECK_IN(g); CHECK_IN(x);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = g.size(1);
-  if (m == 0)  // no rows: the sums over them are zero, nothing to launch
-    return {torch::zeros({n, k}, x.options()),
-            torch::zeros({has_bias ? n : 0}, g.options())};
-  auto dw = torch::empty({n, k}, x.options());
-  torch::Tensor db = torch::empty({0}, g.options());
-  float* db_ptr = nullptr;
-  if (has_bias) {
-    db = torch::empty({n}, g.options());
-    db_ptr = db.data_ptr<float>();
-  }
-  if (prec == 1)
-    launch_gemm_bf16_tn(g.data_ptr<float>(), x.data_ptr<float>(),
-                        dw.data_ptr<float>(), db_ptr, m, n, k, cur_stream());
-  else if (prec == 2)
-    launch_gemm_fp16_tn(g.data_ptr<float>(), x.data_ptr<float>(),
-                        dw.data_ptr<float>(), db_ptr, m, n, k, cur_stream());
-  else
-    launch_gemm_f32_tn(g.data_ptr<float>(), x.data_ptr<float>(),
-                       dw.data_ptr<float>(), db_ptr, m, n, k, cur_stream());
-  return {dw, db};
-}
-
 // both dP tables in one pass over de (h % 256 == 0 required)
 std::vector<torch::Tensor> vocab_scatter_dual(torch::Tensor g,
                                               torch::Tensor ea, int64_t rows0,
@@ -1367,25 +1292,18 @@ std::vector<torch::Tensor> vocab_scatter_dual(torch::Tensor g,
 // bf16-activation-mode linear: fp32 x/w in, bf16 C out; backward from bf16 g
 torch::Tensor linear_fwd_bf16_o16(torch::Tensor x, torch::Tensor w,
                                   torch::Tensor b) {
-  CHECK_IN(x); CHECK_IN(w);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = w.size(0);
+  const auto [m, n, k] = linear_gate("linear_fwd_bf16_o16", LIN_FWD, x,
+                                     torch::kFloat32, w, torch::kFloat32, &b);
   auto y = torch::empty({m, n}, x.options().dtype(torch::kBFloat16));
   if (m == 0) return y;  // no rows: nothing to launch
-  const float* bias = nullptr;
-  if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
-  launch_gemm_bf16_nt_o16(x.data_ptr<float>(), w.data_ptr<float>(), bias,
-                          y.data_ptr(), m, n, k,
-                          cur_stream());
+  launch_gemm_bf16_nt_o16(x.data_ptr<float>(), w.data_ptr<float>(),
+                          bias_ptr(b), y.data_ptr(), m, n, k, cur_stream());
   return y;
 }
 
 torch::Tensor linear_dgrad16(torch::Tensor g, torch::Tensor w) {
-  CHECK_IN(g); CHECK_IN(w);
-  const int m = g.size(0);
-  const int n = w.size(0);
-  const int k = w.size(1);
+  const auto [m, n, k] = linear_gate("linear_dgrad16", LIN_DGRAD, g,
+                                     torch::kBFloat16, w, torch::kFloat32);
   auto dx = torch::empty({m, k}, w.options());
   if (m == 0) return dx;  // no rows: nothing to launch
   if (gemm_dispatch::dgrad_skinny(m)) {  // tiny-row P-table backward
@@ -1407,14 +1325,12 @@ std::vector<torch::Tensor> linear_wgrad16(torch::Tensor g, torch::Tensor x,
                                           OptTensor dw_sink = std::nullopt,
                                           OptTensor db_sink = std::nullopt,
                                           int64_t tile = 0) {
-  CHECK_IN(g); CHECK_IN(x);
   // `tile` as in linear_wgrad16_b16; with fp32 x no shape reaches the glds
   // TN kernel, so none can be forced
   TORCH_CHECK(tile == 0, "linear_wgrad16: fp32 x does not run on the glds TN "
                          "kernel, no tile to force");
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = g.size(1);
+  const auto [m, n, k] = linear_gate("linear_wgrad16", LIN_WGRAD, g,
+                                     torch::kBFloat16, x, torch::kFloat32);
   float* dw_s = grad_sink(dw_sink, x, {n, k}, "linear_wgrad16");
   float* db_s = grad_sink(db_sink, x, {n}, "linear_wgrad16");
   TORCH_CHECK((db_s != nullptr) == (dw_s != nullptr && has_bias),
@@ -1447,135 +1363,6 @@ std::vector<torch::Tensor> linear_wgrad16(torch::Tensor g, torch::Tensor x,
 // Statistics, affine params, weights and weight-grads stay fp32.
 // ---------------------------------------------------------------------------
 
-std::vector<torch::Tensor> bn_relu_fwd16(torch::Tensor x, torch::Tensor gamma,
-                                         torch::Tensor beta,
-                                         torch::Tensor running_mean,
-                                         torch::Tensor running_var,
-                                         double momentum, double eps,
-                                         bool training, bool relu,
-                                         double dropout_p = 0.0,
-                                         torch::Tensor seed = {}) {
-  CHECK_IN(x); CHECK_IN(gamma); CHECK_IN(beta);
-  const long n = x.size(0);
-  const int h = x.size(1);
-  auto fopt = x.options().dtype(torch::kFloat32);
-  auto y = torch::empty({n, h}, x.options().dtype(torch::kBFloat16));
-  auto mean = torch::empty({h}, fopt);
-  auto invstd = torch::empty({h}, fopt);
-  auto partials = torch::empty({2 * h}, fopt);
-  auto slab = training ? bn_wide_slab(x) : torch::empty({0}, fopt);
-  auto mask = bn_new_mask(x, training, relu);
-  const auto* sp = rng_seed_ptr(seed, dropout_p);
-  launch_bn_fwd16(x.data_ptr(), gamma.data_ptr<float>(),
-                  beta.data_ptr<float>(), running_mean.data_ptr<float>(),
-                  running_var.data_ptr<float>(), mean.data_ptr<float>(),
-                  invstd.data_ptr<float>(), partials.data_ptr<float>(),
-                  y.data_ptr(), n, h, (float)momentum, (float)eps, training,
-                  relu, (float)dropout_p, sp, bn_slab_ptr(slab),
-                  mask.numel() ? mask.data_ptr<unsigned char>() : nullptr,
-                  cur_stream());
-  if (sp) launch_counter_bump((unsigned long long*)seed.data_ptr<long>(),
-                              cur_stream());
-  return {y, mean, invstd, mask};
-}
-
-std::vector<torch::Tensor> bn_relu_bwd16(torch::Tensor g, torch::Tensor x,
-                                         torch::Tensor gamma,
-                                         torch::Tensor mean,
-                                         torch::Tensor invstd, torch::Tensor y,
-                                         bool relu, double keep_inv = 1.0,
-                                         OptTensor dgamma_sink = std::nullopt,
-                                         OptTensor dbeta_sink = std::nullopt) {
-  CHECK_IN(g); CHECK_IN(x);
-  const long n = x.size(0);
-  const int h = x.size(1);
-  auto fopt = x.options().dtype(torch::kFloat32);
-  auto dx = torch::empty_like(x);
-  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, "bn_relu_bwd16");
-  auto partials = torch::empty({2 * h}, fopt);
-  auto slab = bn_wide_slab(x);
-  launch_bn_bwd16(g.data_ptr(), x.data_ptr(), y.data_ptr(),
-                  mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                  gamma.data_ptr<float>(), partials.data_ptr<float>(),
-                  dx.data_ptr(), aff.pg, aff.pb, n, h, relu, (float)keep_inv,
-                  bn_slab_ptr(slab), bn_mask_ptr(y, x), cur_stream(), aff.acc);
-  return {dx, aff.dgamma, aff.dbeta};
-}
-
-std::vector<torch::Tensor> bn_finalize_apply16(
-    torch::Tensor x, torch::Tensor partials,
-    torch::Tensor gamma, torch::Tensor beta, torch::Tensor running_mean,
-    torch::Tensor running_var, double momentum, double eps, bool training,
-    bool relu, double dropout_p = 0.0, torch::Tensor seed = {}) {
-  CHECK_IN(x); CHECK_IN(partials);
-  const int h = x.size(1);
-  TORCH_CHECK(partials.numel() == 2 * h + 1,
-              "bn_finalize_apply16 expects [2h+1] partials with the global "
-              "count in the tail slot");
-  auto fopt = x.options().dtype(torch::kFloat32);
-  auto y = torch::empty({x.size(0), h}, x.options().dtype(torch::kBFloat16));
-  auto mean = torch::empty({h}, fopt);
-  auto invstd = torch::empty({h}, fopt);
-  auto mask = bn_new_mask(x, training, relu);
-  const auto* sp = rng_seed_ptr(seed, dropout_p);
-  launch_bn_finalize_apply16(
-      x.data_ptr(), partials.data_ptr<float>(),
-      partials.data_ptr<float>() + 2 * h,
-      gamma.data_ptr<float>(), beta.data_ptr<float>(),
-      running_mean.data_ptr<float>(), running_var.data_ptr<float>(),
-      mean.data_ptr<float>(), invstd.data_ptr<float>(), y.data_ptr(),
-      x.size(0), h, (float)momentum, (float)eps, training, relu,
-      (float)dropout_p, sp,
-      mask.numel() ? mask.data_ptr<unsigned char>() : nullptr, cur_stream());
-  if (sp) launch_counter_bump((unsigned long long*)seed.data_ptr<long>(),
-                              cur_stream());
-  return {y, mean, invstd, mask};
-}
-
-torch::Tensor bn_bwd_partials16(torch::Tensor g, torch::Tensor x,
-                                torch::Tensor y, torch::Tensor mean,
-                                torch::Tensor invstd, bool relu,
-                                double keep_inv = 1.0) {
-  CHECK_IN(g); CHECK_IN(x);
-  const long h = x.size(1);
-  auto partials = torch::empty({2 * h + 1},
-                               x.options().dtype(torch::kFloat32));
-  auto slab = bn_wide_slab(x);
-  launch_bn_bwd_partials_only16(g.data_ptr(), x.data_ptr(),
-                                y.data_ptr(), mean.data_ptr<float>(),
-                                invstd.data_ptr<float>(), x.size(0), h,
-                                relu, partials.data_ptr<float>(),
-                                (float)keep_inv, bn_slab_ptr(slab),
-                                bn_mask_ptr(y, x), cur_stream());
-  partials.narrow(0, 2 * h, 1).fill_((float)x.size(0));
-  return partials;
-}
-
-std::vector<torch::Tensor> bn_bwd_apply16(
-    torch::Tensor g, torch::Tensor x, torch::Tensor y, torch::Tensor mean,
-    torch::Tensor invstd, torch::Tensor gamma, torch::Tensor partials_global,
-    torch::Tensor partials_local, bool relu, double keep_inv = 1.0,
-    OptTensor dgamma_sink = std::nullopt,
-    OptTensor dbeta_sink = std::nullopt) {
-  CHECK_IN(g); CHECK_IN(x);
-  const int h = x.size(1);
-  TORCH_CHECK(partials_global.numel() == 2 * h + 1,
-              "bn_bwd_apply16 expects [2h+1] partials with the global count "
-              "in the tail slot");
-  auto dx = torch::empty_like(x);
-  auto aff = bn_affine_out(dgamma_sink, dbeta_sink, x, h, "bn_bwd_apply16");
-  launch_bn_bwd_apply_only16(g.data_ptr(), x.data_ptr(), y.data_ptr(),
-                             mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                             gamma.data_ptr<float>(),
-                             partials_global.data_ptr<float>(),
-                             partials_global.data_ptr<float>() + 2 * h,
-                             dx.data_ptr(), x.size(0), h, relu,
-                             (float)keep_inv, bn_mask_ptr(y, x), cur_stream());
-  launch_bn_grad_affine(partials_local.data_ptr<float>(), aff.pg, aff.pb, h,
-                        cur_stream(), aff.acc);
-  return {dx, aff.dgamma, aff.dbeta};
-}
-
 // Backward of "fused attention forward -> BN+ReLU(+dropout) forward" in act16
 // mode: g is the gradient of the BN output, x the attention output the BN
 // read, mask the BN forward's keep mask.  The BN partials run as in
@@ -1595,20 +1382,19 @@ std::vector<torch::Tensor> edge_attn_bn_bwd16(
     std::optional<torch::Tensor> partials_local_opt = std::nullopt,
     OptTensor dgamma_sink = std::nullopt,
     OptTensor dbeta_sink = std::nullopt) {
-  CHECK_IN(g); CHECK_IN(x); CHECK_IN(qkvs); CHECK_IN(alpha); CHECK_IN(mask);
-  CHECK_IN(gamma); CHECK_IN(mean); CHECK_IN(invstd);
-  const int n = qkvs.size(0);
-  const int h = qkvs.size(1) / 4;
-  const long ne = ea.size(0);
+  const AttnBwd attn("edge_attn_bn_bwd16", &g, qkvs, pifc, prpc, ea, alpha,
+                     row_ptr, csr_src, col_ptr, csc_dst, csc_eid, heads);
+  const int n = attn.s.n, h = attn.s.h;
+  CHECK_IN(x); CHECK_IN(mask); CHECK_IN(gamma); CHECK_IN(mean);
+  CHECK_IN(invstd);
   TORCH_CHECK(n > 0, "edge_attn_bn_bwd16 needs at least one node");
   TORCH_CHECK(h == 256 || h == 512, "edge_attn_bn_bwd16 covers H = 256, 512");
   TORCH_CHECK(qkvs.scalar_type() == torch::kBFloat16 &&
                   g.scalar_type() == torch::kBFloat16 &&
                   x.scalar_type() == torch::kBFloat16,
               "edge_attn_bn_bwd16 takes bf16 qkvs, g and x");
-  TORCH_CHECK(x.dim() == 2 && x.size(0) == n && x.size(1) == h &&
-                  g.sizes() == x.sizes(),
-              "g and x must be [n, h]");
+  TORCH_CHECK(x.dim() == 2 && x.size(0) == n && x.size(1) == h,
+              "edge_attn_bn_bwd16: x must be [n, h]");
   TORCH_CHECK(mask.scalar_type() == torch::kUInt8,
               "edge_attn_bn_bwd16 needs the BN forward's keep mask");
   TORCH_CHECK(gamma.numel() == h && mean.numel() == h && invstd.numel() == h &&
@@ -1616,13 +1402,6 @@ std::vector<torch::Tensor> edge_attn_bn_bwd16(
                   mean.scalar_type() == torch::kFloat32 &&
                   invstd.scalar_type() == torch::kFloat32,
               "gamma/mean/invstd must be fp32 [h]");
-  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
-              "heads must divide H (H=", h, ", heads=", heads, ")");
-  TORCH_CHECK(alpha.scalar_type() == torch::kFloat32 &&
-                  alpha.numel() == ne * heads,
-              "alpha must be the fp32 [E, heads] tensor of the forward");
-  TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(),
-              "P tables must share a dtype");
   const bool sync = partials_global_opt.has_value();
   TORCH_CHECK(sync == partials_local_opt.has_value(),
               "partials_global and partials_local come together");
@@ -1664,18 +1443,8 @@ std::vector<torch::Tensor> edge_attn_bn_bwd16(
         aff.pb, cur_stream(), aff.acc);
     bn.partials = partials.data_ptr<float>();
   }
-  auto dqkvs = torch::empty_like(qkvs);
-  auto de = torch::empty({ne, h}, qkvs.options());
-  auto dal = torch::empty({ne * heads}, fopt);
-  const int p16 = pifc.scalar_type() == torch::kBFloat16 ? 1 : 0;
-  launch_edge_attn_fused_bwd16(
-      g.data_ptr(), 1, qkvs.data_ptr(), pifc.data_ptr(), prpc.data_ptr(), p16,
-      ea.data_ptr<long>(), (int)ea.size(1), alpha.data_ptr<float>(),
-      row_ptr.data_ptr<int>(), csr_src.data_ptr<int>(),
-      col_ptr.data_ptr<int>(), csc_dst.data_ptr<int>(),
-      csc_eid.data_ptr<int>(), dqkvs.data_ptr(), de.data_ptr(),
-      dal.data_ptr<float>(), n, h, ne, (int)heads, cur_stream(), &bn);
-  return {dqkvs, de, aff.dgamma, aff.dbeta};
+  auto out = attn.run(&bn);
+  return {out[0], out[1], aff.dgamma, aff.dbeta};
 }
 
 // Backward of edge_attention_fused (bf16 qkvs, fp32 output) whose only
@@ -1689,14 +1458,12 @@ std::vector<torch::Tensor> edge_attn_pool_bwd16(
     torch::Tensor prpc, torch::Tensor ea, torch::Tensor alpha,
     torch::Tensor row_ptr, torch::Tensor csr_src, torch::Tensor col_ptr,
     torch::Tensor csc_dst, torch::Tensor csc_eid, int64_t heads = 1) {
+  const AttnBwd attn("edge_attn_pool_bwd16", nullptr, qkvs, pifc, prpc, ea,
+                     alpha, row_ptr, csr_src, col_ptr, csc_dst, csc_eid,
+                     heads);
+  const int n = attn.s.n, h = attn.s.h;
   CHECK_IN(gout); CHECK_IN(probs); CHECK_IN(nn); CHECK_IN(batch);
-  CHECK_IN(qkvs); CHECK_IN(alpha);
-  const int n = qkvs.size(0);
-  const int h = qkvs.size(1) / 4;
-  const long ne = ea.size(0);
   TORCH_CHECK(h == 256 || h == 512, "edge_attn_pool_bwd16 covers H = 256, 512");
-  TORCH_CHECK(qkvs.scalar_type() == torch::kBFloat16,
-              "edge_attn_pool_bwd16 takes bf16 qkvs");
   TORCH_CHECK(gout.scalar_type() == torch::kFloat32 && gout.dim() == 2 &&
                   gout.size(1) == h,
               "gout must be fp32 [graphs, h]");
@@ -1705,32 +1472,12 @@ std::vector<torch::Tensor> edge_attn_pool_bwd16(
                   batch.scalar_type() == torch::kInt64 &&
                   probs.numel() == n && nn.numel() == n && batch.numel() == n,
               "probs/nn (fp32) and batch (int64) must have one entry per node");
-  TORCH_CHECK(heads >= 1 && heads <= h && h % heads == 0,
-              "heads must divide H (H=", h, ", heads=", heads, ")");
-  TORCH_CHECK(alpha.scalar_type() == torch::kFloat32 &&
-                  alpha.numel() == ne * heads,
-              "alpha must be the fp32 [E, heads] tensor of the forward");
-  TORCH_CHECK(pifc.scalar_type() == prpc.scalar_type(),
-              "P tables must share a dtype");
   AttnPoolBwd pool{};
   pool.gout = gout.data_ptr<float>();
   pool.probs = probs.data_ptr<float>();
   pool.nn = nn.data_ptr<float>();
   pool.batch = batch.data_ptr<long>();
-  auto fopt = qkvs.options().dtype(torch::kFloat32);
-  auto dqkvs = torch::empty_like(qkvs);
-  auto de = torch::empty({ne, h}, qkvs.options());
-  auto dal = torch::empty({ne * heads}, fopt);
-  const int p16 = pifc.scalar_type() == torch::kBFloat16 ? 1 : 0;
-  launch_edge_attn_fused_bwd16(
-      nullptr, 0, qkvs.data_ptr(), pifc.data_ptr(), prpc.data_ptr(), p16,
-      ea.data_ptr<long>(), (int)ea.size(1), alpha.data_ptr<float>(),
-      row_ptr.data_ptr<int>(), csr_src.data_ptr<int>(),
-      col_ptr.data_ptr<int>(), csc_dst.data_ptr<int>(),
-      csc_eid.data_ptr<int>(), dqkvs.data_ptr(), de.data_ptr(),
-      dal.data_ptr<float>(), n, h, ne, (int)heads, cur_stream(), nullptr,
-      &pool);
-  return {dqkvs, de};
+  return attn.run(nullptr, &pool);
 }
 
 torch::Tensor seg_pool_fwd16(torch::Tensor x, torch::Tensor probs,
@@ -1738,11 +1485,7 @@ torch::Tensor seg_pool_fwd16(torch::Tensor x, torch::Tensor probs,
                              int64_t num_graphs) {
   CHECK_IN(x); CHECK_IN(probs); CHECK_IN(nn); CHECK_IN(batch_ptr);
   const int h = x.size(1);
-  const long n = x.size(0);
-  long p = 8192 / std::max<int64_t>(num_graphs, 1);
-  const long per_g = (n + std::max<int64_t>(num_graphs, 1) - 1) /
-                     std::max<int64_t>(num_graphs, 1);
-  p = std::min<long>(std::max<long>(std::min(p, per_g), 1), 64);
+  const long p = seg_pool_parts(x.size(0), num_graphs);
   auto fopt = x.options().dtype(torch::kFloat32);
   auto partial = torch::empty({num_graphs * p, h}, fopt);
   auto out = torch::empty({num_graphs, h}, fopt);
@@ -1782,10 +1525,9 @@ static std::vector<torch::Tensor> linear_fwd_a16o16_impl(torch::Tensor x,
                                                          OptTensor out =
                                                              std::nullopt) {
   namespace gd = gemm_dispatch;
-  CHECK_IN(x); CHECK_IN(w);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = w.size(0);
+  const auto [m, n, k] =
+      linear_gate(want_wt ? "linear_fwd_a16o16_wt" : "linear_fwd_a16o16",
+                  LIN_FWD, x, torch::kBFloat16, w, torch::kFloat32, &b);
   // variant != 0 forces the streaming (1) or the A-resident (2) glds kernel
   // for any shape that kernel can run; out, if given, receives y in its
   // first m rows (a test hook: the rows behind them must stay untouched)
@@ -1810,8 +1552,7 @@ static std::vector<torch::Tensor> linear_fwd_a16o16_impl(torch::Tensor x,
   }
   auto wt16 = torch::empty({0}, x.options());
   if (m == 0) return {y, wt16};  // no rows: nothing to launch
-  const float* bias = nullptr;
-  if (b.defined() && b.numel() > 0) bias = b.data_ptr<float>();
+  const float* bias = bias_ptr(b);
   if (fp16c) {
     launch_gemm_fp16_nt_a16o16(x.data_ptr(), w.data_ptr<float>(), bias,
                                y.data_ptr(), m, n, k, cur_stream());
@@ -1879,10 +1620,8 @@ torch::Tensor linear_dgrad16_o16(torch::Tensor g, torch::Tensor w,
                                  bool fp16c = false,
                                  c10::optional<torch::Tensor> wt16_in =
                                      c10::nullopt) {
-  CHECK_IN(g); CHECK_IN(w);
-  const int m = g.size(0);
-  const int n = w.size(0);
-  const int k = w.size(1);
+  const auto [m, n, k] = linear_gate("linear_dgrad16_o16", LIN_DGRAD, g,
+                                     torch::kBFloat16, w, torch::kFloat32);
   auto dx = torch::empty({m, k}, g.options());  // bf16
   if (m == 0) return dx;  // no rows: nothing to launch
   if (fp16c) {
@@ -1923,10 +1662,8 @@ std::vector<torch::Tensor> linear_wgrad16_b16(torch::Tensor g, torch::Tensor x,
                                               OptTensor dw_sink = std::nullopt,
                                               OptTensor db_sink = std::nullopt,
                                               int64_t tile = 0) {
-  CHECK_IN(g); CHECK_IN(x);
-  const int m = x.size(0);
-  const int k = x.size(1);
-  const int n = g.size(1);
+  const auto [m, n, k] = linear_gate("linear_wgrad16_b16", LIN_WGRAD, g,
+                                     torch::kBFloat16, x, torch::kBFloat16);
   // tile != 0 forces an output tile of the glds TN kernel (1 / 2 / 3 =
   // 128x128 / 256x128 / 256x256) for any shape that kernel supports
   const char* det = getenv("PERTGNN_DETERMINISTIC");
@@ -2336,20 +2073,50 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("h"), py::arg("rows"), py::arg("sink") = py::none(),
           py::arg("unroll") = 8, py::arg("seg_cols") = 256);
   mod.def("bn_stats", &bn_stats);
-  mod.def("bn_finalize_apply", &bn_finalize_apply, py::arg("x"),
-          py::arg("partials"), py::arg("gamma"), py::arg("beta"),
-          py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
-          py::arg("eps"), py::arg("training"), py::arg("relu"),
-          py::arg("dropout_p") = 0.0, py::arg("seed") = torch::Tensor());
-  mod.def("bn_bwd_partials", &bn_bwd_partials, py::arg("g"), py::arg("x"),
-          py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("relu"),
-          py::arg("keep_inv") = 1.0);
-  mod.def("bn_bwd_apply", &bn_bwd_apply, py::arg("g"), py::arg("x"),
-          py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
-          py::arg("partials_global"), py::arg("partials_local"),
-          py::arg("relu"), py::arg("keep_inv") = 1.0,
-          py::arg("dgamma_sink") = py::none(),
-          py::arg("dbeta_sink") = py::none());
+  // each BN operation under its fp32 name and its bf16 ("16") name
+  const auto def_bn_fwd = [&mod](const char* name, auto fn) {
+    mod.def(name, fn, py::arg("x"), py::arg("gamma"), py::arg("beta"),
+            py::arg("running_mean"), py::arg("running_var"),
+            py::arg("momentum"), py::arg("eps"), py::arg("training"),
+            py::arg("relu"), py::arg("dropout_p") = 0.0,
+            py::arg("seed") = torch::Tensor());
+  };
+  def_bn_fwd("bn_relu_fwd", &bn_relu_fwd<false>);
+  def_bn_fwd("bn_relu_fwd16", &bn_relu_fwd<true>);
+  const auto def_bn_bwd = [&mod](const char* name, auto fn) {
+    mod.def(name, fn, py::arg("g"), py::arg("x"), py::arg("gamma"),
+            py::arg("mean"), py::arg("invstd"), py::arg("y"), py::arg("relu"),
+            py::arg("keep_inv") = 1.0, py::arg("dgamma_sink") = py::none(),
+            py::arg("dbeta_sink") = py::none());
+  };
+  def_bn_bwd("bn_relu_bwd", &bn_relu_bwd<false>);
+  def_bn_bwd("bn_relu_bwd16", &bn_relu_bwd<true>);
+  const auto def_bn_finalize = [&mod](const char* name, auto fn) {
+    mod.def(name, fn, py::arg("x"), py::arg("partials"), py::arg("gamma"),
+            py::arg("beta"), py::arg("running_mean"), py::arg("running_var"),
+            py::arg("momentum"), py::arg("eps"), py::arg("training"),
+            py::arg("relu"), py::arg("dropout_p") = 0.0,
+            py::arg("seed") = torch::Tensor());
+  };
+  def_bn_finalize("bn_finalize_apply", &bn_finalize_apply<false>);
+  def_bn_finalize("bn_finalize_apply16", &bn_finalize_apply<true>);
+  const auto def_bn_partials = [&mod](const char* name, auto fn) {
+    mod.def(name, fn, py::arg("g"), py::arg("x"), py::arg("y"),
+            py::arg("mean"), py::arg("invstd"), py::arg("relu"),
+            py::arg("keep_inv") = 1.0);
+  };
+  def_bn_partials("bn_bwd_partials", &bn_bwd_partials<false>);
+  def_bn_partials("bn_bwd_partials16", &bn_bwd_partials<true>);
+  const auto def_bn_apply = [&mod](const char* name, auto fn) {
+    mod.def(name, fn, py::arg("g"), py::arg("x"), py::arg("y"),
+            py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
+            py::arg("partials_global"), py::arg("partials_local"),
+            py::arg("relu"), py::arg("keep_inv") = 1.0,
+            py::arg("dgamma_sink") = py::none(),
+            py::arg("dbeta_sink") = py::none());
+  };
+  def_bn_apply("bn_bwd_apply", &bn_bwd_apply<false>);
+  def_bn_apply("bn_bwd_apply16", &bn_bwd_apply<true>);
   mod.def("vocab_scatter", &vocab_scatter);
   mod.def("collate_native", &collate_native,
           py::call_guard<py::gil_scoped_release>());
@@ -2387,30 +2154,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("embed_node_fwd", &embed_node_fwd, py::arg("x_raw"), py::arg("idx"), py::arg("table"), py::arg("out16") = false, py::arg("pad_to") = 0);
   mod.def("embed_edge_fwd", &embed_edge_fwd);
   mod.def("gather_rows", &gather_rows);
-  mod.def("bn_relu_fwd16", &bn_relu_fwd16, py::arg("x"), py::arg("gamma"),
-          py::arg("beta"), py::arg("running_mean"), py::arg("running_var"),
-          py::arg("momentum"), py::arg("eps"), py::arg("training"),
-          py::arg("relu"), py::arg("dropout_p") = 0.0,
-          py::arg("seed") = torch::Tensor());
-  mod.def("bn_relu_bwd16", &bn_relu_bwd16, py::arg("g"), py::arg("x"),
-          py::arg("gamma"), py::arg("mean"), py::arg("invstd"), py::arg("y"),
-          py::arg("relu"), py::arg("keep_inv") = 1.0,
-          py::arg("dgamma_sink") = py::none(),
-          py::arg("dbeta_sink") = py::none());
-  mod.def("bn_finalize_apply16", &bn_finalize_apply16, py::arg("x"),
-          py::arg("partials"), py::arg("gamma"), py::arg("beta"),
-          py::arg("running_mean"), py::arg("running_var"), py::arg("momentum"),
-          py::arg("eps"), py::arg("training"), py::arg("relu"),
-          py::arg("dropout_p") = 0.0, py::arg("seed") = torch::Tensor());
-  mod.def("bn_bwd_partials16", &bn_bwd_partials16, py::arg("g"), py::arg("x"),
-          py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("relu"),
-          py::arg("keep_inv") = 1.0);
-  mod.def("bn_bwd_apply16", &bn_bwd_apply16, py::arg("g"), py::arg("x"),
-          py::arg("y"), py::arg("mean"), py::arg("invstd"), py::arg("gamma"),
-          py::arg("partials_global"), py::arg("partials_local"),
-          py::arg("relu"), py::arg("keep_inv") = 1.0,
-          py::arg("dgamma_sink") = py::none(),
-          py::arg("dbeta_sink") = py::none());
   mod.def("edge_attn_bn_bwd16", &edge_attn_bn_bwd16, py::arg("g"),
           py::arg("x"), py::arg("mask"), py::arg("gamma"), py::arg("mean"),
           py::arg("invstd"), py::arg("keep_inv"), py::arg("qkvs"),
@@ -2452,16 +2195,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
           py::arg("n"), py::arg("k"), py::arg("io"), py::arg("prec"),
           py::arg("deterministic") = false);
   mod.def("linear_path_labels", &linear_path_labels);
-  mod.def("bn_relu_fwd", &bn_relu_fwd, py::arg("x"), py::arg("gamma"),
-          py::arg("beta"), py::arg("running_mean"), py::arg("running_var"),
-          py::arg("momentum"), py::arg("eps"), py::arg("training"),
-          py::arg("relu"), py::arg("dropout_p") = 0.0,
-          py::arg("seed") = torch::Tensor());
-  mod.def("bn_relu_bwd", &bn_relu_bwd, py::arg("g"), py::arg("x"),
-          py::arg("gamma"), py::arg("mean"), py::arg("invstd"), py::arg("y"),
-          py::arg("relu"), py::arg("keep_inv") = 1.0,
-          py::arg("dgamma_sink") = py::none(),
-          py::arg("dbeta_sink") = py::none());
   mod.def("quantile_loss_fwd", &quantile_loss_fwd);
   mod.def("quantile_loss_bwd", &quantile_loss_bwd);
   mod.def("eval_metrics", &eval_metrics);

@@ -15,6 +15,7 @@
 // (VPT = ceil(H/64) <= 8 register slots per lane).
 
 #include "common.h"
+#include "launchers.h"
 #include <cmath>
 
 #define WAVES_PER_BLOCK 4

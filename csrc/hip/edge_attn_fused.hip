@@ -26,6 +26,7 @@
 // dP_ifc/dP_rpc.  Deterministic — no atomics anywhere.
 
 #include "common.h"
+#include "launchers.h"
 #include "attn_bn.h"
 #include <cmath>
 #include <cstdlib>

@@ -17,6 +17,7 @@
 // (16 lanes read 16 consecutive floats of one LDS row).
 
 #include "common.h"
+#include "launchers.h"
 #include "gemm_dispatch.h"
 #include <cstdlib>
 

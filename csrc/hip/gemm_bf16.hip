@@ -10,6 +10,7 @@
 // makes the 16-lane fragment reads conflict-free (guide §6 G4).
 
 #include "common.h"
+#include "launchers.h"
 #include "gemm_dispatch.h"
 
 // PERTGNN_DETERMINISTIC=1: collapse split-K wgrad to one slice so the dw/db

@@ -6,7 +6,9 @@
 //   K12/K13 quantile loss + eval-metric reductions
 //   K14     Adam step (flat master buffers — one kernel for the whole model)
 #include "common.h"
+#include "launchers.h"
 #include <cstdlib>
+#include <type_traits>
 
 // ---------------------------------------------------------------------------
 // pattern pool: out[b] = sum_{i in graph b} x[i] * p[i] / n[i]
@@ -1002,12 +1004,28 @@ __global__ void vocab_scatter_priv_kernel(const GT* __restrict__ g,
   }
 }
 
-// bf16-gradient variant: wave-private path only (the caller upcasts to f32
-// when the private tables do not fit)
-void launch_vocab_scatter16(const void* g_v, const long* idx, long idx_stride,
-                            float* dtable, long n, int rows, int h,
-                            int gstride, int col_off, hipStream_t s) {
-  const __bf16* g = (const __bf16*)g_v;
+template <int HH, typename GT>
+static void vocab_priv_launch(const GT* g, const long* idx, long idx_stride,
+                              float* dtable, long n, int rows, int h,
+                              int gstride, int col_off, int blocks, size_t lds,
+                              hipStream_t s) {
+  HIP_CHECK(hipFuncSetAttribute(
+      (const void*)vocab_scatter_priv_kernel<4, HH, GT>,
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  vocab_scatter_priv_kernel<4, HH, GT>
+      <<<dim3(max(blocks, 1), h / HH), dim3(WAVES_PER_BLOCK * PERTGNN_WAVE),
+         lds, s>>>(g, idx, idx_stride, dtable, n, rows, h, gstride, col_off);
+}
+
+// GT = float (launch_vocab_scatter) or __bf16 (launch_vocab_scatter16).  The
+// wave-private kernel takes either; the whole-table kernels behind it are
+// fp32 only, so a bf16 gradient whose private tables do not fit is an error
+// (the caller upcasts it to f32)
+template <typename GT>
+static void vocab_scatter_launch(const GT* g, const long* idx,
+                                 long idx_stride, float* dtable, long n,
+                                 int rows, int h, int gstride, int col_off,
+                                 hipStream_t s) {
   HIP_CHECK(hipMemsetAsync(dtable, 0, (long)rows * h * sizeof(float), s));
   if (n == 0) return;
   // block count scaled inversely with table size: each extra block
@@ -1015,87 +1033,57 @@ void launch_vocab_scatter16(const void* g_v, const long* idx, long idx_stride,
   // rows) need far more than 128 blocks to occupy 256 CUs (measured
   // 1 wave/SIMD at the old cap)
   const long merge_cap = (long)1000000 / (long)max(rows * 128, 1);
-  const int blocks =
+  const int pblocks =
       (int)min((n + 255) / 256, max((long)128, min((long)768, merge_cap)));
   const size_t lds128 = (size_t)WAVES_PER_BLOCK * rows * 128 * sizeof(float);
   const size_t lds64 = (size_t)WAVES_PER_BLOCK * rows * 64 * sizeof(float);
   if (h % 128 == 0 && lds128 <= 160 * 1024) {
-    HIP_CHECK(hipFuncSetAttribute(
-        (const void*)vocab_scatter_priv_kernel<4, 128, __bf16>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128));
-    vocab_scatter_priv_kernel<4, 128, __bf16>
-        <<<dim3(max(blocks, 1), h / 128), dim3(WAVES_PER_BLOCK * PERTGNN_WAVE),
-           lds128, s>>>(g, idx, idx_stride, dtable, n, rows, h, gstride,
-                        col_off);
+    vocab_priv_launch<128>(g, idx, idx_stride, dtable, n, rows, h, gstride,
+                           col_off, pblocks, lds128, s);
     return;
   }
   if (h % 64 == 0 && lds64 <= 160 * 1024) {
-    HIP_CHECK(hipFuncSetAttribute(
-        (const void*)vocab_scatter_priv_kernel<4, 64, __bf16>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
-    vocab_scatter_priv_kernel<4, 64, __bf16>
-        <<<dim3(max(blocks, 1), h / 64), dim3(WAVES_PER_BLOCK * PERTGNN_WAVE),
-           lds64, s>>>(g, idx, idx_stride, dtable, n, rows, h, gstride,
-                       col_off);
+    vocab_priv_launch<64>(g, idx, idx_stride, dtable, n, rows, h, gstride,
+                          col_off, pblocks, lds64, s);
     return;
   }
-  pertgnn_shape_fail("vocab_scatter", "table_bytes_over_lds_h", h);  // caller guarantees fit (python upcasts otherwise)
+  if constexpr (!std::is_same_v<GT, float>) {
+    pertgnn_shape_fail("vocab_scatter", "table_bytes_over_lds_h", h);
+  } else {
+    const size_t lds = (size_t)rows * h * sizeof(float);
+    const bool vec = (h % (4 * PERTGNN_WAVE) == 0) && ((gstride & 3) == 0) &&
+                     ((col_off & 3) == 0);
+    const void* fn = vec ? (const void*)vocab_scatter_vec_kernel
+                         : (const void*)vocab_scatter_kernel;
+    if (lds > 64 * 1024) {
+      HIP_CHECK(hipFuncSetAttribute(
+          fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    const int blocks = (int)min((long)256, (n + 63) / 64);
+    if (vec)
+      vocab_scatter_vec_kernel<<<dim3(blocks),
+                                 dim3(WAVES_PER_BLOCK * PERTGNN_WAVE), lds,
+                                 s>>>(g, idx, idx_stride, dtable, n, rows, h,
+                                      gstride, col_off);
+    else
+      vocab_scatter_kernel<<<dim3(blocks),
+                             dim3(WAVES_PER_BLOCK * PERTGNN_WAVE), lds, s>>>(
+          g, idx, idx_stride, dtable, n, rows, h, gstride, col_off);
+  }
 }
 
 void launch_vocab_scatter(const float* g, const long* idx, long idx_stride,
                           float* dtable, long n, int rows, int h, int gstride,
                           int col_off, hipStream_t s) {
-  HIP_CHECK(hipMemsetAsync(dtable, 0, (long)rows * h * sizeof(float), s));
-  if (n == 0) return;
-  {
-    // block count scaled inversely with table size: each extra block
-    // costs a table-sized atomic merge, but small tables (rpctype ~5
-    // rows) need far more than 128 blocks to occupy 256 CUs (measured
-    // 1 wave/SIMD at the old cap)
-    const long merge_cap = (long)1000000 / (long)max(rows * 128, 1);
-    const int blocks =
-        (int)min((n + 255) / 256, max((long)128, min((long)768, merge_cap)));
-    const size_t lds128 = (size_t)WAVES_PER_BLOCK * rows * 128 * sizeof(float);
-    const size_t lds64 = (size_t)WAVES_PER_BLOCK * rows * 64 * sizeof(float);
-    if (h % 128 == 0 && lds128 <= 160 * 1024) {
-      HIP_CHECK(hipFuncSetAttribute(
-          (const void*)vocab_scatter_priv_kernel<4, 128>,
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds128));
-      vocab_scatter_priv_kernel<4, 128>
-          <<<dim3(max(blocks, 1), h / 128),
-             dim3(WAVES_PER_BLOCK * PERTGNN_WAVE), lds128, s>>>(
-              g, idx, idx_stride, dtable, n, rows, h, gstride, col_off);
-      return;
-    }
-    if (h % 64 == 0 && lds64 <= 160 * 1024) {
-      HIP_CHECK(hipFuncSetAttribute(
-          (const void*)vocab_scatter_priv_kernel<4, 64>,
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds64));
-      vocab_scatter_priv_kernel<4, 64>
-          <<<dim3(max(blocks, 1), h / 64),
-             dim3(WAVES_PER_BLOCK * PERTGNN_WAVE), lds64, s>>>(
-              g, idx, idx_stride, dtable, n, rows, h, gstride, col_off);
-      return;
-    }
-  }
-  const size_t lds = (size_t)rows * h * sizeof(float);
-  const bool vec = (h % (4 * PERTGNN_WAVE) == 0) && ((gstride & 3) == 0) &&
-                   ((col_off & 3) == 0);
-  const void* fn = vec ? (const void*)vocab_scatter_vec_kernel
-                       : (const void*)vocab_scatter_kernel;
-  if (lds > 64 * 1024) {
-    HIP_CHECK(hipFuncSetAttribute(
-        fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  const int blocks = (int)min((long)256, (n + 63) / 64);
-  if (vec)
-    vocab_scatter_vec_kernel<<<dim3(blocks),
-                               dim3(WAVES_PER_BLOCK * PERTGNN_WAVE), lds, s>>>(
-        g, idx, idx_stride, dtable, n, rows, h, gstride, col_off);
-  else
-    vocab_scatter_kernel<<<dim3(blocks), dim3(WAVES_PER_BLOCK * PERTGNN_WAVE),
-                           lds, s>>>(g, idx, idx_stride, dtable, n, rows, h,
-                                     gstride, col_off);
+  vocab_scatter_launch(g, idx, idx_stride, dtable, n, rows, h, gstride,
+                       col_off, s);
+}
+
+void launch_vocab_scatter16(const void* g, const long* idx, long idx_stride,
+                            float* dtable, long n, int rows, int h,
+                            int gstride, int col_off, hipStream_t s) {
+  vocab_scatter_launch((const __bf16*)g, idx, idx_stride, dtable, n, rows, h,
+                       gstride, col_off, s);
 }
 
 // entry embedding gather: out[b] = table[idx[b]] — plain gather (fwd) +
@@ -2124,12 +2112,18 @@ void launch_bn_eval_stats(const float* running_mean, const float* running_var,
                                                         invstd, h, eps);
 }
 
-// --- granular launchers for sync-BN (partials are all-reduced across ranks
-// between the stats and apply phases; `count` = GLOBAL row count) ---
+// --- BN launchers.  Each operation is one template over the activation
+// dtype T: float (launch_bn_*) or __bf16 (launch_bn_*16, the act16 mode: x,
+// y, the incoming grad g and dx are bf16; statistics, affine params and
+// their grads stay fp32 — standard mixed-precision BN).  The keep mask and
+// the 8-wide apply kernels exist for bf16 only.  The granular ones serve
+// sync-BN: partials are all-reduced across ranks between the stats and apply
+// phases, and `count_ptr` holds the GLOBAL row count. ---
 
 // slab: [bn_wide_slab_rows(n, h), 2h] per-call scratch (nullptr when that
 // returns 0) — same convention for every reduction launcher below
-void launch_bn_stats_only(const float* x, long n, int h, float* partials,
+template <typename T>
+static void bn_stats_only(const T* x, long n, int h, float* partials,
                           float* slab, hipStream_t s) {
   if (n == 0) {
     HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
@@ -2143,76 +2137,38 @@ void launch_bn_stats_only(const float* x, long n, int h, float* partials,
   bn_stats_dispatch(x, n, h, partials, s);
 }
 
-void launch_bn_finalize_apply(const float* x, const float* partials,
-                              const float* count_ptr, const float* gamma,
-                              const float* beta, float* running_mean,
-                              float* running_var, float* mean, float* invstd,
-                              float* y, long n, int h, float momentum,
-                              float eps, bool training, bool relu,
-                              float dropout_p,
-                              const unsigned long long* seed_ptr,
-                              hipStream_t s) {
-  if (training) {
-    bn_finalize_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
-        partials, n, h, eps, momentum, mean, invstd, running_mean,
-        running_var, 1, count_ptr);
-  } else {
-    bn_eval_stats_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
-        running_mean, running_var, mean, invstd, h, eps);
+// the element-wise forward over [n, h], n > 0; a mask selects the 8-wide
+// kernel that also writes it
+template <typename T>
+static void bn_apply_launch(const T* x, const float* mean, const float* invstd,
+                            const float* gamma, const float* beta, T* y,
+                            unsigned char* mask, long n, int h, bool training,
+                            bool relu, float dropout_p,
+                            const unsigned long long* seed_ptr,
+                            hipStream_t s) {
+  if constexpr (std::is_same_v<T, __bf16>) {
+    if (mask) {
+      bn_apply_mask_launch(x, mean, invstd, gamma, beta, y, mask, n, h,
+                           dropout_p, seed_ptr, s);
+      return;
+    }
   }
-  if (n > 0) {
-    if (training && dropout_p > 0.f)
-      bn_apply_kernel<float, float, true><<<grid_for(n * h), 256, 0, s>>>(
-          x, mean, invstd, gamma, beta, y, n, h, relu ? 1 : 0, dropout_p,
-          seed_ptr);
-    else
-      bn_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(x, mean, invstd, gamma,
-                                                      beta, y, n, h,
-                                                      relu ? 1 : 0);
-  }
+  if (training && dropout_p > 0.f)
+    bn_apply_kernel<T, T, true><<<grid_for(n * h), 256, 0, s>>>(
+        x, mean, invstd, gamma, beta, y, n, h, relu ? 1 : 0, dropout_p,
+        seed_ptr);
+  else
+    bn_apply_kernel<T, T, false><<<grid_for(n * h), 256, 0, s>>>(
+        x, mean, invstd, gamma, beta, y, n, h, relu ? 1 : 0);
 }
 
-void launch_bn_bwd_partials_only(const float* g, const float* x,
-                                 const float* y, const float* mean,
-                                 const float* invstd, long n, int h, bool relu,
-                                 float* partials, float keep_inv,
-                                 float* slab, hipStream_t s) {
-  if (n == 0) {
-    HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
-    return;
-  }
-  if (bn_wide_ok(h)) {
-    bn_bwd_partials_wide_launch(g, x, y, nullptr, mean, invstd, n, h, relu,
-                                partials, slab, nullptr, nullptr, keep_inv, s);
-    return;
-  }
-  bn_bwd_partials_dispatch(g, x, y, mean, invstd, n, h, relu, partials,
-                           keep_inv, s);
-}
-
-void launch_bn_bwd_apply_only(const float* g, const float* x, const float* y,
-                              const float* mean, const float* invstd,
-                              const float* gamma, const float* partials,
-                              const float* count_ptr, float* dx, long n, int h,
-                              bool relu, float keep_inv, hipStream_t s) {
-  if (n == 0) return;
-  bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
-      g, x, y, mean, invstd, gamma, partials, dx, n, n, h, relu ? 1 : 0,
-      count_ptr, keep_inv);
-}
-
-void launch_bn_grad_affine(const float* partials, float* dgamma, float* dbeta,
-                           int h, hipStream_t s, bool acc) {
-  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
-      partials, dgamma, dbeta, h, acc ? 1 : 0);
-}
-
-void launch_bn_fwd(const float* x, const float* gamma, const float* beta,
+template <typename T>
+static void bn_fwd(const T* x, const float* gamma, const float* beta,
                    float* running_mean, float* running_var, float* mean,
-                   float* invstd, float* partials, float* y, long n, int h,
+                   float* invstd, float* partials, T* y, long n, int h,
                    float momentum, float eps, bool training, bool relu,
                    float dropout_p, const unsigned long long* seed_ptr,
-                   float* slab, hipStream_t s) {
+                   float* slab, unsigned char* mask, hipStream_t s) {
   if (n == 0) return;
   if (training && bn_wide_ok(h)) {
     bn_stats_wide_launch(x, n, h, partials, slab, true, eps, momentum, mean,
@@ -2225,94 +2181,144 @@ void launch_bn_fwd(const float* x, const float* gamma, const float* beta,
   } else {
     launch_bn_eval_stats(running_mean, running_var, mean, invstd, h, eps, s);
   }
-  if (training && dropout_p > 0.f)
-    bn_apply_kernel<float, float, true><<<grid_for(n * h), 256, 0, s>>>(
-        x, mean, invstd, gamma, beta, y, n, h, relu ? 1 : 0, dropout_p,
-        seed_ptr);
-  else
-    bn_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(x, mean, invstd, gamma,
-                                                    beta, y, n, h,
-                                                    relu ? 1 : 0);
+  bn_apply_launch(x, mean, invstd, gamma, beta, y, mask, n, h, training, relu,
+                  dropout_p, seed_ptr, s);
 }
 
-void launch_counter_bump(unsigned long long* c, hipStream_t s) {
-  counter_bump_kernel<<<1, 1, 0, s>>>(c);
+template <typename T>
+static void bn_finalize_apply(const T* x, const float* partials,
+                              const float* count_ptr, const float* gamma,
+                              const float* beta, float* running_mean,
+                              float* running_var, float* mean, float* invstd,
+                              T* y, long n, int h, float momentum, float eps,
+                              bool training, bool relu, float dropout_p,
+                              const unsigned long long* seed_ptr,
+                              unsigned char* mask, hipStream_t s) {
+  if (training) {
+    bn_finalize_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+        partials, n, h, eps, momentum, mean, invstd, running_mean,
+        running_var, 1, count_ptr);
+  } else {
+    bn_eval_stats_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+        running_mean, running_var, mean, invstd, h, eps);
+  }
+  if (n > 0)
+    bn_apply_launch(x, mean, invstd, gamma, beta, y, mask, n, h, training,
+                    relu, dropout_p, seed_ptr, s);
 }
 
-void launch_bn_bwd(const float* g, const float* x, const float* y,
-                   const float* mean, const float* invstd, const float* gamma,
-                   float* partials, float* dx, float* dgamma, float* dbeta,
-                   long n, int h, bool relu, float keep_inv, float* slab,
-                   hipStream_t s, bool acc) {
-  if (n == 0) return;
-  const bool wide = bn_wide_ok(h);
-  if (wide)
-    bn_bwd_partials_wide_launch(g, x, y, nullptr, mean, invstd, n, h, relu,
-                                partials, slab, dgamma, dbeta, keep_inv, s,
-                                acc);
-  else
-    bn_bwd_partials_dispatch(g, x, y, mean, invstd, n, h, relu, partials,
-                             keep_inv, s);
-  bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
-      g, x, y, mean, invstd, gamma, partials, dx, n, n, h, relu ? 1 : 0,
-      nullptr, keep_inv);
-  if (wide) return;  // dgamma/dbeta written with the partials
-  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
-      partials, dgamma, dbeta, h, acc ? 1 : 0);
-}
-
-// --- act16 launchers: fully bf16 activation streams — x (the conv output /
-// BN input), y, incoming grad g, and dx are all bf16; statistics, affine
-// params and their grads stay fp32 (standard mixed-precision BN). ---
-
-void launch_bn_stats_only16(const void* x, long n, int h, float* partials,
-                            float* slab, hipStream_t s) {
+template <typename T>
+static void bn_bwd_partials_only(const T* g, const T* x, const T* y,
+                                 const float* mean, const float* invstd,
+                                 long n, int h, bool relu, float* partials,
+                                 float keep_inv, float* slab,
+                                 const unsigned char* mask, hipStream_t s) {
   if (n == 0) {
     HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
     return;
   }
   if (bn_wide_ok(h)) {
-    bn_stats_wide_launch((const __bf16*)x, n, h, partials, slab, false, 0.f,
-                         0.f, nullptr, nullptr, nullptr, nullptr, s);
+    bn_bwd_partials_wide_launch(g, x, y, mask, mean, invstd, n, h, relu,
+                                partials, slab, nullptr, nullptr, keep_inv, s);
     return;
   }
-  bn_stats_dispatch((const __bf16*)x, n, h, partials, s);
+  bn_bwd_partials_dispatch(g, x, y, mean, invstd, n, h, relu, partials,
+                           keep_inv, s);
 }
 
+// the element-wise backward over [n, h], n > 0 (count_ptr null: count is n)
+template <typename T>
+static void bn_bwd_apply_launch(const T* g, const T* x, const T* y,
+                                const float* mean, const float* invstd,
+                                const float* gamma, const float* partials,
+                                const float* count_ptr, T* dx, long n, int h,
+                                bool relu, float keep_inv,
+                                const unsigned char* mask, hipStream_t s) {
+  if constexpr (std::is_same_v<T, __bf16>) {
+    if (relu && bn_wide_ok(h)) {
+      if (mask)
+        bn_bwd_apply_wide_kernel<2><<<grid_for(n * (h / 8)), 256, 0, s>>>(
+            g, x, mask, mean, invstd, gamma, partials, dx, n, n, h, count_ptr,
+            keep_inv);
+      else
+        bn_bwd_apply_wide_kernel<1><<<grid_for(n * (h / 8)), 256, 0, s>>>(
+            g, x, y, mean, invstd, gamma, partials, dx, n, n, h, count_ptr,
+            keep_inv);
+      return;
+    }
+  }
+  bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
+      g, x, y, mean, invstd, gamma, partials, dx, n, n, h, relu ? 1 : 0,
+      count_ptr, keep_inv);
+}
+
+template <typename T>
+static void bn_bwd(const T* g, const T* x, const T* y, const float* mean,
+                   const float* invstd, const float* gamma, float* partials,
+                   T* dx, float* dgamma, float* dbeta, long n, int h,
+                   bool relu, float keep_inv, float* slab,
+                   const unsigned char* mask, hipStream_t s, bool acc) {
+  if (n == 0) return;
+  const bool wide = bn_wide_ok(h);
+  if (wide)
+    bn_bwd_partials_wide_launch(g, x, y, mask, mean, invstd, n, h, relu,
+                                partials, slab, dgamma, dbeta, keep_inv, s,
+                                acc);
+  else
+    bn_bwd_partials_dispatch(g, x, y, mean, invstd, n, h, relu, partials,
+                             keep_inv, s);
+  bn_bwd_apply_launch(g, x, y, mean, invstd, gamma, partials, nullptr, dx, n,
+                      h, relu, keep_inv, mask, s);
+  if (wide) return;  // dgamma/dbeta written with the partials
+  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+      partials, dgamma, dbeta, h, acc ? 1 : 0);
+}
+
+// --- the extern names (launchers.h): fp32 has no keep mask ---
+
+void launch_bn_stats_only(const float* x, long n, int h, float* partials,
+                          float* slab, hipStream_t s) {
+  bn_stats_only(x, n, h, partials, slab, s);
+}
+void launch_bn_stats_only16(const void* x, long n, int h, float* partials,
+                            float* slab, hipStream_t s) {
+  bn_stats_only((const __bf16*)x, n, h, partials, slab, s);
+}
+
+void launch_bn_fwd(const float* x, const float* gamma, const float* beta,
+                   float* running_mean, float* running_var, float* mean,
+                   float* invstd, float* partials, float* y, long n, int h,
+                   float momentum, float eps, bool training, bool relu,
+                   float dropout_p, const unsigned long long* seed_ptr,
+                   float* slab, hipStream_t s) {
+  bn_fwd(x, gamma, beta, running_mean, running_var, mean, invstd, partials, y,
+         n, h, momentum, eps, training, relu, dropout_p, seed_ptr, slab,
+         nullptr, s);
+}
 void launch_bn_fwd16(const void* x, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, float* mean,
                      float* invstd, float* partials, void* y, long n, int h,
                      float momentum, float eps, bool training, bool relu,
                      float dropout_p, const unsigned long long* seed_ptr,
                      float* slab, unsigned char* mask, hipStream_t s) {
-  if (n == 0) return;
-  if (training && bn_wide_ok(h)) {
-    bn_stats_wide_launch((const __bf16*)x, n, h, partials, slab, true, eps,
-                         momentum, mean, invstd, running_mean, running_var, s);
-  } else if (training) {
-    bn_stats_dispatch((const __bf16*)x, n, h, partials, s);
-    bn_finalize_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
-        partials, n, h, eps, momentum, mean, invstd, running_mean, running_var,
-        1);
-  } else {
-    launch_bn_eval_stats(running_mean, running_var, mean, invstd, h, eps, s);
-  }
-  if (mask) {
-    bn_apply_mask_launch((const __bf16*)x, mean, invstd, gamma, beta,
-                         (__bf16*)y, mask, n, h, dropout_p, seed_ptr, s);
-    return;
-  }
-  if (training && dropout_p > 0.f)
-    bn_apply_kernel<__bf16, __bf16, true><<<grid_for(n * h), 256, 0, s>>>(
-        (const __bf16*)x, mean, invstd, gamma, beta, (__bf16*)y, n, h,
-        relu ? 1 : 0, dropout_p, seed_ptr);
-  else
-    bn_apply_kernel<<<grid_for(n * h), 256, 0, s>>>((const __bf16*)x, mean,
-                                                    invstd, gamma, beta,
-                                                    (__bf16*)y, n, h,
-                                                    relu ? 1 : 0);
+  bn_fwd((const __bf16*)x, gamma, beta, running_mean, running_var, mean,
+         invstd, partials, (__bf16*)y, n, h, momentum, eps, training, relu,
+         dropout_p, seed_ptr, slab, mask, s);
 }
 
+void launch_bn_finalize_apply(const float* x, const float* partials,
+                              const float* count_ptr, const float* gamma,
+                              const float* beta, float* running_mean,
+                              float* running_var, float* mean, float* invstd,
+                              float* y, long n, int h, float momentum,
+                              float eps, bool training, bool relu,
+                              float dropout_p,
+                              const unsigned long long* seed_ptr,
+                              hipStream_t s) {
+  bn_finalize_apply(x, partials, count_ptr, gamma, beta, running_mean,
+                    running_var, mean, invstd, y, n, h, momentum, eps,
+                    training, relu, dropout_p, seed_ptr, nullptr, s);
+}
 void launch_bn_finalize_apply16(const void* x, const float* partials,
                                 const float* count_ptr, const float* gamma,
                                 const float* beta, float* running_mean,
@@ -2322,50 +2328,29 @@ void launch_bn_finalize_apply16(const void* x, const float* partials,
                                 float dropout_p,
                                 const unsigned long long* seed_ptr,
                                 unsigned char* mask, hipStream_t s) {
-  if (training) {
-    bn_finalize_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
-        partials, n, h, eps, momentum, mean, invstd, running_mean,
-        running_var, 1, count_ptr);
-  } else {
-    bn_eval_stats_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
-        running_mean, running_var, mean, invstd, h, eps);
-  }
-  if (n > 0 && mask) {
-    bn_apply_mask_launch((const __bf16*)x, mean, invstd, gamma, beta,
-                         (__bf16*)y, mask, n, h, dropout_p, seed_ptr, s);
-  } else if (n > 0) {
-    if (training && dropout_p > 0.f)
-      bn_apply_kernel<__bf16, __bf16, true><<<grid_for(n * h), 256, 0, s>>>(
-          (const __bf16*)x, mean, invstd, gamma, beta, (__bf16*)y, n, h,
-          relu ? 1 : 0, dropout_p, seed_ptr);
-    else
-      bn_apply_kernel<<<grid_for(n * h), 256, 0, s>>>((const __bf16*)x, mean,
-                                                      invstd, gamma, beta,
-                                                      (__bf16*)y, n, h,
-                                                      relu ? 1 : 0);
-  }
+  bn_finalize_apply((const __bf16*)x, partials, count_ptr, gamma, beta,
+                    running_mean, running_var, mean, invstd, (__bf16*)y, n, h,
+                    momentum, eps, training, relu, dropout_p, seed_ptr, mask,
+                    s);
 }
 
+void launch_bn_bwd_partials_only(const float* g, const float* x,
+                                 const float* y, const float* mean,
+                                 const float* invstd, long n, int h, bool relu,
+                                 float* partials, float keep_inv,
+                                 float* slab, hipStream_t s) {
+  bn_bwd_partials_only(g, x, y, mean, invstd, n, h, relu, partials, keep_inv,
+                       slab, nullptr, s);
+}
 void launch_bn_bwd_partials_only16(const void* g, const void* x,
                                    const void* y, const float* mean,
                                    const float* invstd, long n, int h,
                                    bool relu, float* partials, float keep_inv,
                                    float* slab, const unsigned char* mask,
                                    hipStream_t s) {
-  if (n == 0) {
-    HIP_CHECK(hipMemsetAsync(partials, 0, 2 * h * sizeof(float), s));
-    return;
-  }
-  if (bn_wide_ok(h)) {
-    bn_bwd_partials_wide_launch((const __bf16*)g, (const __bf16*)x,
-                                (const __bf16*)y, mask, mean, invstd, n, h,
-                                relu, partials, slab, nullptr, nullptr,
-                                keep_inv, s);
-    return;
-  }
-  bn_bwd_partials_dispatch((const __bf16*)g, (const __bf16*)x,
-                           (const __bf16*)y, mean, invstd, n, h, relu,
-                           partials, keep_inv, s);
+  bn_bwd_partials_only((const __bf16*)g, (const __bf16*)x, (const __bf16*)y,
+                       mean, invstd, n, h, relu, partials, keep_inv, slab,
+                       mask, s);
 }
 
 // first half of launch_bn_bwd16 on the keep-mask path (training forward with
@@ -2386,6 +2371,15 @@ void launch_bn_bwd_partials_affine16(const void* g, const void* x,
                               keep_inv, s, acc);
 }
 
+void launch_bn_bwd_apply_only(const float* g, const float* x, const float* y,
+                              const float* mean, const float* invstd,
+                              const float* gamma, const float* partials,
+                              const float* count_ptr, float* dx, long n, int h,
+                              bool relu, float keep_inv, hipStream_t s) {
+  if (n == 0) return;
+  bn_bwd_apply_launch(g, x, y, mean, invstd, gamma, partials, count_ptr, dx, n,
+                      h, relu, keep_inv, nullptr, s);
+}
 void launch_bn_bwd_apply_only16(const void* g, const void* x, const void* y,
                                 const float* mean, const float* invstd,
                                 const float* gamma, const float* partials,
@@ -2393,56 +2387,38 @@ void launch_bn_bwd_apply_only16(const void* g, const void* x, const void* y,
                                 int h, bool relu, float keep_inv,
                                 const unsigned char* mask, hipStream_t s) {
   if (n == 0) return;
-  if (relu && bn_wide_ok(h)) {
-    if (mask)
-      bn_bwd_apply_wide_kernel<2><<<grid_for(n * (h / 8)), 256, 0, s>>>(
-          (const __bf16*)g, (const __bf16*)x, mask, mean, invstd, gamma,
-          partials, (__bf16*)dx, n, n, h, count_ptr, keep_inv);
-    else
-      bn_bwd_apply_wide_kernel<1><<<grid_for(n * (h / 8)), 256, 0, s>>>(
-          (const __bf16*)g, (const __bf16*)x, y, mean, invstd, gamma,
-          partials, (__bf16*)dx, n, n, h, count_ptr, keep_inv);
-    return;
-  }
-  bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
-      (const __bf16*)g, (const __bf16*)x, (const __bf16*)y, mean, invstd,
-      gamma, partials, (__bf16*)dx, n, n, h, relu ? 1 : 0, count_ptr,
-      keep_inv);
+  bn_bwd_apply_launch((const __bf16*)g, (const __bf16*)x, (const __bf16*)y,
+                      mean, invstd, gamma, partials, count_ptr, (__bf16*)dx, n,
+                      h, relu, keep_inv, mask, s);
 }
 
+void launch_bn_grad_affine(const float* partials, float* dgamma, float* dbeta,
+                           int h, hipStream_t s, bool acc) {
+  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
+      partials, dgamma, dbeta, h, acc ? 1 : 0);
+}
+
+void launch_counter_bump(unsigned long long* c, hipStream_t s) {
+  counter_bump_kernel<<<1, 1, 0, s>>>(c);
+}
+
+void launch_bn_bwd(const float* g, const float* x, const float* y,
+                   const float* mean, const float* invstd, const float* gamma,
+                   float* partials, float* dx, float* dgamma, float* dbeta,
+                   long n, int h, bool relu, float keep_inv, float* slab,
+                   hipStream_t s, bool acc) {
+  bn_bwd(g, x, y, mean, invstd, gamma, partials, dx, dgamma, dbeta, n, h, relu,
+         keep_inv, slab, nullptr, s, acc);
+}
 void launch_bn_bwd16(const void* g, const void* x, const void* y,
                      const float* mean, const float* invstd,
                      const float* gamma, float* partials, void* dx,
                      float* dgamma, float* dbeta, long n, int h, bool relu,
                      float keep_inv, float* slab, const unsigned char* mask,
                      hipStream_t s, bool acc) {
-  if (n == 0) return;
-  const bool wide = bn_wide_ok(h);
-  if (wide)
-    bn_bwd_partials_wide_launch((const __bf16*)g, (const __bf16*)x,
-                                (const __bf16*)y, mask, mean, invstd, n, h,
-                                relu, partials, slab, dgamma, dbeta, keep_inv,
-                                s, acc);
-  else
-    bn_bwd_partials_dispatch((const __bf16*)g, (const __bf16*)x,
-                             (const __bf16*)y, mean, invstd, n, h, relu,
-                             partials, keep_inv, s);
-  if (relu && wide && mask)
-    bn_bwd_apply_wide_kernel<2><<<grid_for(n * (h / 8)), 256, 0, s>>>(
-        (const __bf16*)g, (const __bf16*)x, mask, mean, invstd, gamma,
-        partials, (__bf16*)dx, n, n, h, nullptr, keep_inv);
-  else if (relu && wide)
-    bn_bwd_apply_wide_kernel<1><<<grid_for(n * (h / 8)), 256, 0, s>>>(
-        (const __bf16*)g, (const __bf16*)x, y, mean, invstd, gamma, partials,
-        (__bf16*)dx, n, n, h, nullptr, keep_inv);
-  else
-    bn_bwd_apply_kernel<<<grid_for(n * h), 256, 0, s>>>(
-        (const __bf16*)g, (const __bf16*)x, (const __bf16*)y, mean, invstd,
-        gamma, partials, (__bf16*)dx, n, n, h, relu ? 1 : 0, nullptr,
-        keep_inv);
-  if (wide) return;  // dgamma/dbeta written with the partials
-  bn_grad_affine_kernel<<<ceil_div(h, 256), 256, 0, s>>>(
-      partials, dgamma, dbeta, h, acc ? 1 : 0);
+  bn_bwd((const __bf16*)g, (const __bf16*)x, (const __bf16*)y, mean, invstd,
+         gamma, partials, (__bf16*)dx, dgamma, dbeta, n, h, relu, keep_inv,
+         slab, mask, s, acc);
 }
 
 // ---------------------------------------------------------------------------
